@@ -12,6 +12,13 @@ after the timed region's batches (§8(e)), over RCCL.
 
 Prints ONE JSON line (rank 0).
 
+A plain run (`--gpus 1 --steps N --warmup W`) sets up, warms up, times the N
+steps and prints the line; `--dump-outputs DIR` also writes what the last timed
+step computed (dump_outputs).  Everything measured beside the headline -- the
+unbucketed, two-stream and large-contract C2 fields, the roofline profile, the
+LaserEVM fields, C3, C4, the CPU baselines and the full record -- runs only
+with `--full`.
+
 Multi-GPU: `python bench.py --gpus N` with no WORLD_SIZE in the environment
 starts N rank processes itself (one per GPU, RANK/LOCAL_RANK/WORLD_SIZE set,
 rendezvous on 127.0.0.1) before anything touches a GPU, and exits with their
@@ -39,6 +46,13 @@ def parse(argv=None):
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--lanes", type=int, default=65536)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the secondary C2 fields, the roofline "
+                         "profile, the LaserEVM fields, C3, C4 and the CPU baselines (each has its own "
+                         "switch below); without it only the warm-up and the timed C2 steps run")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step left in the lanes as "
+                         "DIR/<name>.npy (float32 / float64; see dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--c4-dags", type=int, default=1_000_000)
@@ -183,7 +197,7 @@ def main(argv=None, device_factory=None, backend: str = "nccl"):
     from mythril_amd.lanes import bucket_order, permuted
     dev.alloc(batch.shape, coverage=True)
     unbucketed = None
-    if args.unbucketed_steps and not args.profile_only:
+    if args.full and args.unbucketed_steps and not args.profile_only:
         # the same lanes in generation order: what bucketing buys (reported
         # beside `value`, never as it)
         _log(rank, "C2 unbucketed")
@@ -223,13 +237,17 @@ def main(argv=None, device_factory=None, backend: str = "nccl"):
     elapsed, total_steps = mdist.reduce_timing(elapsed, float(lane_steps))
     total_steps = int(total_steps)
 
+    if args.dump_outputs and rank == 0 and args.steps:
+        _log(rank, f"writing the last timed step's outputs to {args.dump_outputs}")
+        dump_outputs(dev, batch.shape, stats[-1], dev.coverage(cid), args.dump_outputs)
+
     overlap = None
-    if args.overlap_steps and gpu and not args.profile_only:
+    if args.full and args.overlap_steps and gpu and not args.profile_only:
         _log(rank, "C2 on two streams")
         overlap = run_two_streams(dev, batch, code, args.overlap_steps, local, barrier)
 
     large = None
-    if args.large_steps and not args.profile_only:
+    if args.full and args.large_steps and not args.profile_only:
         _log(rank, "C2 on the 3,523-instruction fixture")
         large = run_large(dev, args, rank, barrier)
         # back to the C2 batch for the roofline profile below
@@ -237,7 +255,7 @@ def main(argv=None, device_factory=None, backend: str = "nccl"):
         dev.upload(workloads.slim_copy(batch))
 
     roof = None
-    if rank == 0 and not args.profile_only and not args.no_roofline:
+    if args.full and rank == 0 and not args.profile_only and not args.no_roofline:
         _log(rank, "C2 roofline profile")
         roof = roofline.lane_step_roofline(dev, batch, cid, kernel_ms=float(np.mean(kernel_ms)) if kernel_ms else 0.0)
 
@@ -261,28 +279,28 @@ def main(argv=None, device_factory=None, backend: str = "nccl"):
             Path(args.host_profile, f"{name}.txt").write_text(buf.getvalue())
 
     hooked = None
-    if args.hooked_lanes and gpu and not args.profile_only:
+    if args.full and args.hooked_lanes and gpu and not args.profile_only:
         _log(rank, f"hooked C2 ({args.hooked_lanes} lanes)")
         hooked = host_profiled("hooked_c2", lambda: run_hooked_c2(dev, args.hooked_lanes, rank))
 
     taint = None
-    if args.taint_lanes and gpu and not args.profile_only:
+    if args.full and args.taint_lanes and gpu and not args.profile_only:
         _log(rank, f"taint C2 ({args.taint_lanes} lanes)")
         taint = host_profiled("taint_c2", lambda: run_taint_c2(dev, args.taint_lanes, rank,
                                                                   tuple(args.taint_modes.split(","))))
 
     symlanes = None
-    if args.symbolic_lanes and gpu and not args.profile_only:
+    if args.full and args.symbolic_lanes and gpu and not args.profile_only:
         _log(rank, f"symbolic lanes ({args.symbolic_lanes}) on k_sym_step")
         symlanes = run_symbolic_lanes(dev, args.symbolic_lanes)
 
     taintlanes = None
-    if args.symbolic_lanes and gpu and not args.profile_only:
+    if args.full and args.symbolic_lanes and gpu and not args.profile_only:
         _log(rank, f"taint lanes ({args.symbolic_lanes}) on k_sym_step")
         taintlanes = run_taint_lanes(dev, args.symbolic_lanes, rank)
 
     symb = None
-    if args.symbolic_replicas and gpu and not args.profile_only:
+    if args.full and args.symbolic_replicas and gpu and not args.profile_only:
         _log(rank, f"symbolic transactions (-t {args.symbolic_tx}, {args.symbolic_replicas} replicas)")
         sys.path.insert(0, str(ROOT / "tests"))
         import symref
@@ -291,17 +309,17 @@ def main(argv=None, device_factory=None, backend: str = "nccl"):
             escape_handler=symref.Engine(signals=True).step))
 
     analyses = None
-    if args.analyses and gpu and not args.profile_only:
+    if args.full and args.analyses and gpu and not args.profile_only:
         _log(rank, f"myth analyze over the 18 contracts (-t {args.analyses})")
         analyses = host_profiled("myth_analyze", lambda: run_myth_analyze(
             dev, args.analyses, log=lambda m: _log(rank, m), cpu=not args.no_cpu_baseline))
 
     c3 = None
-    if args.c3_tx and gpu and not args.profile_only and rank == 0:
+    if args.full and args.c3_tx and gpu and not args.profile_only and rank == 0:
         c3 = host_profiled("c3_bectoken", lambda: run_c3_bectoken(dev, args.c3_tx, log=lambda m: _log(rank, m)))
 
     c4 = None
-    if not args.no_c4:
+    if args.full and not args.no_c4:
         _log(rank, "C4")
         c4 = run_c4(args, dev, rank, world, barrier, dist_on)
 
@@ -341,7 +359,7 @@ def main(argv=None, device_factory=None, backend: str = "nccl"):
             out["c2_two_streams"] = overlap
         if large is not None:
             out["c2_large_contract"] = large
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             from oracle import cpu_baseline
             _log(rank, "C2 CPU baseline")
             out["cpu_baseline"] = cpu_baseline.c2_lane_steps(code, args.cpu_seconds)
@@ -365,15 +383,70 @@ def main(argv=None, device_factory=None, backend: str = "nccl"):
             out["myth_analyze"] = analyses
         if c3 is not None:
             out["c3_bectoken"] = c3
-        full = Path(args.full_record)
-        try:
-            full.parent.mkdir(parents=True, exist_ok=True)
-            full.write_text(json.dumps(out, indent=1) + "\n")
-        except OSError as e:
-            _log(rank, f"full record not written ({e})")
-        print(json.dumps(compact_line(out, str(args.full_record))), flush=True)
+        if args.full:
+            full = Path(args.full_record)
+            try:
+                full.parent.mkdir(parents=True, exist_ok=True)
+                full.write_text(json.dumps(out, indent=1) + "\n")
+            except OSError as e:
+                _log(rank, f"full record not written ({e})")
+        print(json.dumps(compact_line(out, str(args.full_record) if args.full else None)), flush=True)
     if dist_on:
         dist.destroy_process_group()
+
+
+DUMP_SEED = 0x44554D50
+DUMP_SAMPLE = 4096          # lanes whose stack, memory, storage and records are written
+DUMP_STACK_WORDS = 64
+DUMP_LIMIT = 60_000_000     # bytes over all files
+
+
+def dump_outputs(dev, shape, last, coverage, directory) -> None:
+    """What a caller of the timed path holds after its last step, as
+    `directory`/<name>.npy: the step's statistics (`step_stats`: lane_steps,
+    running, halted, hooked, escaped), the coverage bytes of the code, and the
+    lanes downloaded from the device -- every lane's parity scalars
+    (lanes.PARITY_SCALARS, the return range of lanes that returned or
+    reverted), and for a fixed seeded sample of lanes (`sample_lanes`) the
+    stack below sp (its lowest DUMP_STACK_WORDS words), memory below msize, the
+    storage entries and the function-manager records in use.  What lies past
+    those lengths is not a result (lanes.diff_batches) and is written as 0.
+    u32 limbs and u64 gas go to float64 (exact below 2**53), bytes to float32."""
+    from mythril_amd.lanes import MG_HALT_RETURN, MG_HALT_REVERT, PARITY_SCALARS, LaneBatch
+    out = LaneBatch(shape)
+    dev.download(out)
+    n = shape.n
+    d = Path(directory)
+    d.mkdir(parents=True, exist_ok=True)
+    files = {"step_stats": np.array([last.lane_steps, last.running, last.halted, last.hooked, last.escaped],
+                                    dtype=np.float64),
+             "coverage": np.asarray(coverage, dtype=np.float32)}
+    for f in PARITY_SCALARS:
+        if f != "trace_len" or shape.trace_cap:
+            files[f] = getattr(out, f).astype(np.float64)
+    returned = (out.status == MG_HALT_RETURN) | (out.status == MG_HALT_REVERT)
+    files["ret_offset"] = np.where(returned, out.ret_offset, 0).astype(np.float64)
+    files["ret_len"] = np.where(returned, out.ret_len, 0).astype(np.float64)
+    words = min(shape.stack_cap, DUMP_STACK_WORDS)
+    k = min(n, DUMP_SAMPLE)
+    fixed = sum(a.nbytes for a in files.values())
+    per_lane = 8 + words * 8 * 8 + shape.mem_cap * 4 + shape.storage_cap * 16 * 8 + max(shape.rec_cap, 1) * 8
+    while k > 1 and fixed + k * per_lane > DUMP_LIMIT:
+        k //= 2
+    idx = np.sort(np.random.Generator(np.random.PCG64(DUMP_SEED)).choice(n, size=k, replace=False))
+    files["sample_lanes"] = idx.astype(np.float64)
+
+    def below(rows, lengths):
+        """rows[i, j, ...] for j < lengths[i], else 0."""
+        keep = np.arange(rows.shape[1])[None, :] < lengths[:, None]
+        return np.where(keep.reshape(keep.shape + (1,) * (rows.ndim - 2)), rows, 0)
+    files["stack"] = below(out.stack[idx, :words], out.sp[idx]).astype(np.float64)
+    files["memory"] = below(out.memory[idx], out.msize[idx]).astype(np.float32)
+    files["storage"] = below(out.storage[idx], out.storage_count[idx]).astype(np.float64)
+    if shape.rec_cap:
+        files["rec"] = below(out.rec[idx], out.rec_len[idx]).astype(np.float64)
+    for name, arr in files.items():
+        np.save(d / f"{name}.npy", arr)
 
 
 LINE_LIMIT = 4096
