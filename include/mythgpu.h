@@ -61,7 +61,8 @@ extern "C" {
                                   symbolic operands (pops only)
                               15: function-entry tracking (mg_lane_soa.fent,
                                   mg_code_fentries): the last JUMP / JUMPI landing
-                                  on a dispatcher entry, for active_function_name */
+                                  on a dispatcher entry, for active_function_name;
+                                  additive: mg_eval_terms, mg_eval_min */
 
 /* ------------------------------------------------------------------ errors */
 #define MG_OK          0
@@ -607,6 +608,41 @@ int         mg_eval_upload(mg_ctx *ctx, const mg_dag_batch *dags, const mg_model
 int         mg_eval_run(mg_ctx *ctx, uint32_t dag_first, uint32_t dag_count, float *kernel_ms);
 int         mg_eval_download(mg_ctx *ctx, uint32_t *first_sat_model, uint32_t *sat_count,
                              uint32_t dag_first, uint32_t dag_count);
+
+/* Term values.  Replaces model.eval(expr, model_completion=True) of a term
+ * under a model (analysis/solver.py:88-93, 191-194), for every (program, model)
+ * pair in one launch: values[d][m] = the final accumulator of program d under
+ * model m, 8 little-endian 32-bit limbs (a Boolean program leaves 0 or 1).
+ * The values (n_dags x n_models x 32 bytes) must stay under 4 GiB (32-bit
+ * offsets in the kernels), else MG_EINVAL.                                   */
+int         mg_eval_terms(mg_ctx *ctx, const mg_dag_batch *dags, const mg_model_batch *models,
+                          uint32_t *values /* [n_dags][n_models][8] */, float *kernel_ms);
+
+/* Lexicographic minimum over the candidate models.  Replaces Optimize.minimize
+ * per term + check (support/model.py:56-82; get_transaction_sequence's calldata
+ * sizes and call values in priority order, analysis/solver.py:219-259) over the
+ * pool: per query, a model is a candidate when every constraint program listed
+ * for it evaluates to true (no program listed: every model), and the winner is
+ * the candidate with the smallest objective tuple -- each objective an unsigned
+ * 256-bit number, the tuple compared in list order, ties to the smallest model
+ * index.  Constraint and objective programs are DAGs of the one `dags` batch.
+ * best_model[q] = the winner (UINT32_MAX: no candidate, then every limb of its
+ * values is all-ones), best_values[obj_off[q] + j] = its j-th objective,
+ * cand_count[q] = the number of candidates.  Offsets start at 0 and do not
+ * decrease, indices are below n_dags, a query lists at most MG_MIN_OBJ
+ * objectives: anything else is MG_EINVAL before any launch.                  */
+#define MG_MIN_OBJ 8u
+typedef struct mg_min_batch {
+    uint32_t n_queries, _pad;
+    const uint32_t *cons_off;  /* [n_queries+1] into cons_dag                          */
+    const uint32_t *cons_dag;  /* DAG indices that must all evaluate to true            */
+    const uint32_t *obj_off;   /* [n_queries+1] into obj_dag; <= MG_MIN_OBJ per query   */
+    const uint32_t *obj_dag;   /* DAG indices of the minimised terms, most significant first */
+} mg_min_batch;
+int         mg_eval_min(mg_ctx *ctx, const mg_dag_batch *dags, const mg_model_batch *models,
+                        const mg_min_batch *queries, uint32_t *best_model,
+                        uint32_t *best_values /* [obj_off[n_queries]][8] */, uint32_t *cand_count,
+                        float *kernel_ms);
 
 /* ------------------------------------------------------ conjunct compiler */
 /* Kernel 2's register programs compiled on the host from lowered constraint

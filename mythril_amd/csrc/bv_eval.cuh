@@ -99,6 +99,11 @@ struct BvState {
     size_t cap_entries = 0;
     std::vector<uint32_t> h_tiles;
     std::vector<uint32_t> h_insns, h_off;   // the fused programs (bv_fuse)
+    uint4 *term_values = nullptr;    // [n_dags][n_models][2] scratch of k_bv_terms (mg_eval_terms / mg_eval_min)
+    size_t cap_terms = 0;
+    uint32_t *min_buf = nullptr;     // mg_eval_min: the query lists, then the results (bv_lexmin)
+    size_t cap_min = 0;
+    std::vector<uint32_t> h_min;
 };
 
 DEV U256 bv_mask(U256 v, uint32_t width) {
@@ -378,249 +383,99 @@ __global__ BV_BOUNDS void k_bv_eval(const uint4 *__restrict__ insns,
                                                       uint32_t *__restrict__ sat_count,
                                                       unsigned long long *__restrict__ sat_bits,
                                                       uint32_t bit_words) {
-    extern __shared__ __attribute__((aligned(16))) uint4 smem[];
-    // instructions are read with scalar loads (uniform address -> s_load_dwordx4
-    // through the scalar cache); LDS holds only the register slots.  Staging the
-    // program tile in LDS measured slower (occupancy, ab/k2_lds_fetch.diff)
-    uint4 *slots = smem;                         // [n_slots][2][BV_BLOCK]
-    // group-major order with the tile count padded to a multiple of 8: the blocks
-    // of one program tile share blockIdx % 8, i.e. one XCD's L2 (speed only)
-    const uint32_t b = blockIdx.x;
-    const uint32_t tile = tile_first + (b % tiles_pad);
-    const uint32_t group = b / tiles_pad;
-    if (tile >= tile_first + n_tiles) return;
-    const uint32_t d0 = max(tile_dag[tile], dag_lo), d1 = min(tile_dag[tile + 1], dag_hi);
-    if (d0 >= d1) return;
-    // the tile is read from HBM once per block and reused for every model chunk
-    const uint32_t i0 = prog_off[d0], i1 = prog_off[d1];
-    // per-block results of the tile's DAGs: waves combine in LDS, the block adds
-    // its totals to HBM once per DAG (not one atomic pair per wave per DAG)
-    __shared__ uint32_t blk_cnt[BV_TILE_DAGS], blk_first[BV_TILE_DAGS];
-    if (threadIdx.x < BV_TILE_DAGS) { blk_cnt[threadIdx.x] = 0u; blk_first[threadIdx.x] = 0xffffffffu; }
-    __syncthreads();
+#define BV_TERMS 0
+#include "bv_interp.cuh"
+#undef BV_TERMS
+}
 
-    const uint32_t n_chunks = (n_models + BV_BLOCK - 1u) / BV_BLOCK;
-    const uint32_t c_lo = group * chunks_per_block, c_hi = min(c_lo + chunks_per_block, n_chunks);
-    // thread index = the wave's first (an SGPR) + the lane id (v_mbcnt): nothing
-    // keeps threadIdx.x alive across the loops
-    const uint32_t wave0 = uni(threadIdx.x) & ~63u;
-    // this thread's column of the slot table (tid = m % BV_BLOCK = wave0 + lane for every
-    // chunk): a slot access adds only the slot's uniform offset
-    uint4 *const lane_slots = slots + wave0 + __lane_id();
-    // DAG-major: one DAG's program (tens of instructions) is evaluated for all of
-    // the block's model chunks while it is hot in the scalar cache; chunk-major
-    // re-read the whole tile (up to 32 KiB) once per chunk, which the scalar
-    // cache cannot hold and a CU's resident blocks' tiles overflow L2 with
-    for (uint32_t d = d0; d < d1; ++d) {
-    const uint32_t p0 = prog_off[d] - i0, p1 = prog_off[d + 1] - i0;
-    for (uint32_t chunk = c_lo; chunk < c_hi; ++chunk) {
-        BvCtx c{values, consts, lane_slots, n_models, chunk * BV_BLOCK + wave0 + __lane_id(), tab};
-        U256 acc = u_zero();
-        // byte offsets into the tile (32-bit, wave-uniform): the scalar load takes the
-        // offset as its SGPR operand instead of a 64-bit address computed per instruction
-        const char *const tileb = reinterpret_cast<const char *>(insns + i0);
-        for (uint32_t off = p0 << 4, off_end = p1 << 4; off < off_end; off += 16u) {
-            // c.m is the only per-lane context.  Round 3 hid its loop invariance
-            // (an empty asm on it here) because min(m, n - 1) and m % 256 kept in
-            // VGPRs across the loop spilled; with the predecoded dispatch the
-            // kernel fits without it (62 VGPRs, no scratch) and runs 1.9 % faster
-            // with them hoisted (profiles/r05/k2/ab_k2_q.log)
-            uint32_t w0, ra, rb, rc;
-            {
-                const uint4 ins = *reinterpret_cast<const uint4 *>(tileb + uni(off));
-                w0 = ins.x; ra = ins.y; rb = ins.z; rc = ins.w;
-            }
-            // op byte bit 7 = one operand (bv_predecode); w0 bit 30 = mask to width
-            const uint32_t op = w0 & 0x3fu, width = (w0 >> 8) & 0x1ffu;
-            if ((ra >> 30) != BV_REF_ACC) acc = bv_fetch(c, ra);    // A in the accumulator's registers
-            const U256 A = acc;
-            U256 r;
-            if (w0 & BV_W0_UNARY) {
-                if (w0 & BV_W0_HOT) {
-                    r = u_shr_u(A, rb & 0xffu, 0u);                              // BV_EXTRACT
-                } else {
-                switch (op) {
-                case BV_NOT: r = u_not(A); break;
-                case BV_NEG: r = u_neg(A); break;
-                case BV_BNOT: r = u_small((A.w[0] & 1u) ^ 1u); break;
-                case BV_SEXT: r = bv_sext(A, rb); break;
-                default: r = A; break;                                          // BV_COPY, BV_ZEXT
-                }
-                }
-            } else {
-                U256 B = bv_fetch(c, rb);
-                if (w0 & BV_W0_HOT) {                        // BV_CMP_BAND
-                    const uint32_t sub = (w0 >> 22) & 0x3fu;
-                    bool t;
-                    switch (sub) {
-                    case BV_EQ: t = bv_eq(A, B); break;
-                    case BV_NE: t = !bv_eq(A, B); break;
-                    case BV_ULT: t = u_lt(A, B); break;
-                    case BV_ULE: t = !u_lt(B, A); break;
-                    case BV_UGT: t = u_lt(B, A); break;
-                    case BV_UGE: t = !u_lt(A, B); break;
-                    case BV_SLT: t = u_slt(bv_sext(A, width), bv_sext(B, width)); break;
-                    case BV_SLE: t = !u_slt(bv_sext(B, width), bv_sext(A, width)); break;
-                    case BV_SGT: t = u_slt(bv_sext(B, width), bv_sext(A, width)); break;
-                    default: t = !u_slt(bv_sext(A, width), bv_sext(B, width)); break;   // BV_SGE
-                    }
-                    const U256 C = bv_fetch(c, rc);
-                    r = u_small((t ? 1u : 0u) & C.w[0]);
-                } else if (op == BV_UDIV || op == BV_UREM) {        // the unsigned division site
-                    r = bv_udivrem(op == BV_UDIV, A, B);
-                } else if ((BV_DIV_OPS >> op) & 1ull) {      // the signed / overflow site
-                    r = bv_divop(op, width, rc, A, B);
-                } else {
-                switch (op) {
-                case BV_ADD: r = u_add(A, B); break;
-                case BV_SUB: r = u_sub(A, B); break;
-                case BV_MUL: r = u_mul(A, B); break;
-                case BV_AND: r = u_and(A, B); break;
-                case BV_OR: r = u_or(A, B); break;
-                case BV_XOR: r = u_xor(A, B); break;
-                case BV_SHL: case BV_LSHR: case BV_ASHR: {
-                    // a constant shift amount is wave-uniform: scalar-branch shifts
-                    const bool ub = (rb >> 30) == BV_REF_CONST;
-                    const bool in = bv_fits32(B) && B.w[0] < width;
-                    if (op == BV_ASHR) {
-                        const U256 sa = bv_sext(A, width);
-                        const uint32_t fill = u_isneg(sa) ? 0xffffffffu : 0u;
-                        if (ub) {
-                            const uint32_t sh = uni(in ? B.w[0] : 255u);
-                            r = u_shr_u(sa, sh, fill);
-                        } else {
-                            r = u_shr_n(sa, in ? B.w[0] : 255u, fill);
-                        }
-                    } else if (ub) {
-                        if (!uni(in ? 1u : 0u)) r = u_zero();
-                        else if (op == BV_SHL) r = u_shl_u(A, uni(B.w[0]));
-                        else r = u_shr_u(A, uni(B.w[0]), 0u);
-                    } else {
-                        r = !in ? u_zero() : op == BV_SHL ? u_shl_n(A, B.w[0]) : u_shr_n(A, B.w[0], 0u);
-                    }
-                    break;
-                }
-                case BV_EQ: r = u_small(bv_eq(A, B)); break;
-                case BV_NE: r = u_small(!bv_eq(A, B)); break;
-                case BV_ULT: r = u_small(u_lt(A, B)); break;
-                case BV_ULE: r = u_small(!u_lt(B, A)); break;
-                case BV_UGT: r = u_small(u_lt(B, A)); break;
-                case BV_UGE: r = u_small(!u_lt(A, B)); break;
-                case BV_SLT: r = u_small(u_slt(bv_sext(A, rc), bv_sext(B, rc))); break;
-                case BV_SLE: r = u_small(!u_slt(bv_sext(B, rc), bv_sext(A, rc))); break;
-                case BV_SGT: r = u_small(u_slt(bv_sext(B, rc), bv_sext(A, rc))); break;
-                case BV_SGE: r = u_small(!u_slt(bv_sext(A, rc), bv_sext(B, rc))); break;
-                case BV_BAND: r = u_small(A.w[0] & B.w[0] & 1u); break;
-                case BV_BOR: r = u_small((A.w[0] | B.w[0]) & 1u); break;
-                case BV_BXOR: r = u_small((A.w[0] ^ B.w[0]) & 1u); break;
-                case BV_BIMPLIES: r = u_small(((A.w[0] & 1u) ^ 1u) | (B.w[0] & 1u)); break;
-                case BV_ITE: {
-                    const U256 C = bv_fetch(c, rc);
-                    r = u_select((A.w[0] & 1u) != 0u, B, C);
-                    break;
-                }
-                case BV_CONCAT: r = u_or(u_shl_u(A, rc), B); break;                 // rc: uniform
-                case BV_ADD_NOOVF_U: {  // top bit of the (w+1)-bit sum is 0
-                    const U256 s = u_add(A, B);
-                    const bool ovf = rc >= 256u ? u_lt(s, A) : !bv_iszero(u_shr_u(s, rc, 0u));
-                    r = u_small(!ovf);
-                    break;
-                }
-                case BV_SUB_NOUDF_U: r = u_small(!u_lt(A, B)); break;
-                case BV_TAB: r = bv_table(c, A, B, rc); break;
-                case BV_UMIN: r = u_select(u_lt(B, A), B, A); break;
-                case BV_UMAX: r = u_select(u_lt(A, B), B, A); break;
-                case BV_SMIN: r = u_select(u_slt(bv_sext(B, width), bv_sext(A, width)), B, A); break;
-                case BV_SMAX: r = u_select(u_slt(bv_sext(A, width), bv_sext(B, width)), B, A); break;
-                case BV_RSUB: r = u_sub(B, A); break;
-                case BV_RCONCAT: r = u_or(u_shl_u(B, rc), A); break;
-                case BV_BIN2: {
-                    const U256 t = bv_simple((w0 >> 22) & 0xfu, A, B);
-                    const U256 C = bv_fetch(c, rc);
-                    r = bv_simple((w0 >> 26) & 0xfu, t, C);
-                    break;
-                }
-                case BV_BINX: {
-                    uint32_t e0, e1, e2;
-                    {
-                        const uint4 x = *reinterpret_cast<const uint4 *>(tileb + uni(off + 16u));
-                        e0 = x.x; e1 = x.y; e2 = x.z;
-                    }
-                    off += 16u;                              // the extension slot
-                    const uint32_t k = (w0 >> 22) & 0x7u;
-                    U256 t = bv_simple(e0 & 0xfu, A, B);
-#pragma unroll 1
-                    for (uint32_t j = 1; j < k; ++j) {
-                        const uint32_t ref = j == 1u ? rc : j == 2u ? e1 : e2;
-                        const U256 C = bv_fetch(c, ref);
-                        t = bv_simple((e0 >> (4u * j)) & 0xfu, t, C);
-                    }
-                    r = t;
-                    break;
-                }
-                case BV_EXT_RCAT: {
-                    const uint32_t ew = (rc >> 17) & 0x1ffu;
-                    U256 lo = u_shr_u(A, (rc >> 9) & 0xffu, 0u);
-                    if (ew < 256u) lo = bv_mask(lo, ew);
-                    r = u_or(u_shl_u(B, rc & 0x1ffu), lo);
-                    break;
-                }
-                default: r = u_zero(); break;
-                }
-            }
-            }
-            // mask, fused tail and store in one test for the common instruction
-            // that has none of them
-            if (w0 & (BV_W0_MASK | (1u << 31) | (1u << 17))) {
-                // the result masked to its width first (a tail's ops are 256-bit)
-                if (w0 & BV_W0_MASK) r = bv_mask(r, width);
-                if (w0 >> 31) {
-                    // fused tail (bv_fuse): 1-3 bv_simple ops applied to this result,
-                    // from an extension slot {kinds | count << 28, B1, B2, B3}
-                    uint32_t e0, e1, e2, e3;
-                    {
-                        const uint4 x = *reinterpret_cast<const uint4 *>(tileb + uni(off + 16u));
-                        e0 = x.x; e1 = x.y; e2 = x.z; e3 = x.w;
-                    }
-                    off += 16u;
-                    const uint32_t k = e0 >> 28;
-#pragma unroll 1
-                    for (uint32_t j = 0; j < k; ++j) {
-                        const uint32_t ref = j == 0u ? e1 : j == 1u ? e2 : e3;
-                        const U256 C = bv_fetch(c, ref);
-                        r = bv_simple((e0 >> (4u * j)) & 0xfu, r, C);
-                    }
-                }
-                if ((w0 >> 17) & 1u) {
-                    const uint32_t ds = (w0 >> 18) & 0xfu;
-                    lane_slots[(ds * 2u) * BV_BLOCK] = make_uint4(r.w[0], r.w[1], r.w[2], r.w[3]);
-                    lane_slots[(ds * 2u + 1u) * BV_BLOCK] = make_uint4(r.w[4], r.w[5], r.w[6], r.w[7]);
-                }
-            }
-            acc = r;
-        }
-        const bool sat = c.m < n_models && (acc.w[0] & 1u);
-        const uint64_t bal = __ballot(sat);
-        // the wave's first model, wave-uniform (an SGPR: nothing per lane stays live
-        // across the DAG loop but c.m and the accumulator)
-        const uint32_t wm = uni(c.m) & ~63u;
-        if (bal && __lane_id() == 0u) {
-            // optional per-model bitmap (one u64 per wave): lets the host replay
-            // sequential check_quick_sat calls whose LRU bumps reorder the pool
-            if (sat_bits) sat_bits[(size_t)d * bit_words + (wm >> 6)] = bal;
-            atomicAdd(&blk_cnt[d - d0], (uint32_t)__popcll(bal));
-            atomicMin(&blk_first[d - d0], wm + (uint32_t)(__ffsll((long long)bal) - 1));
-        }
+// Term values: the same interpreter (bv_interp.cuh), each lane's final
+// accumulator written out instead of balloted (Model.eval of a term under every
+// candidate model).
+__global__ BV_BOUNDS void k_bv_terms(const uint4 *__restrict__ insns,
+                                     const uint32_t *__restrict__ prog_off,
+                                     const uint32_t *__restrict__ tile_dag,
+                                     const uint4 *__restrict__ consts,
+                                     const uint4 *__restrict__ values, uint32_t n_models,
+                                     BvTables tab,
+                                     uint32_t n_slots, uint32_t tile_first, uint32_t n_tiles,
+                                     uint32_t tiles_pad, uint32_t dag_lo, uint32_t dag_hi,
+                                     uint32_t tile_cap, uint32_t chunks_per_block,
+                                     uint4 *__restrict__ term_values) {
+#define BV_TERMS 1
+#include "bv_interp.cuh"
+#undef BV_TERMS
+}
+
+// Lexicographic minimum over candidate models (z3 Optimize.minimize in priority
+// order + check, support/model.py:56-82, over the pool instead of a search): one
+// block per query, over the value rows k_bv_terms wrote.  A model is a candidate
+// when bit 0 of every constraint DAG of the query is 1; the winner has the
+// smallest objective tuple (each objective an unsigned 256-bit number, limb 7
+// most significant; the tuple compared left to right), ties to the smallest
+// model index.  One block-wide reduction of (tuple, index): a thread carries only
+// the INDEX of its best model and compares two models by reading their rows
+// (k <= 8 objectives would be 64 VGPRs per tuple; these launches are small and
+// latency-bound) -- over its strided models first, then across the wave's 64
+// lanes by shuffles of the index, then across the block's waves through LDS.
+#define BV_NO_MODEL 0xffffffffu
+struct BvMinQuery {
+    const uint4 *__restrict__ values;        // [n_dags][n_models][2]
+    const uint32_t *__restrict__ obj;        // the query's objective DAGs
+    uint32_t n_obj, n_models;
+    DEV const uint4 *row(uint32_t dag, uint32_t m) const {
+        return reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(values) + (dag * n_models + m) * 32u);
     }
+    // is model a's (tuple, index) smaller than b's?  BV_NO_MODEL is larger than any model
+    DEV bool less(uint32_t a, uint32_t b) const {
+        if (a == BV_NO_MODEL || b == BV_NO_MODEL) return a != BV_NO_MODEL;
+        if (a == b) return false;
+        for (uint32_t j = 0; j < n_obj; ++j) {
+            const uint32_t dag = obj[j];
+            const U256 x = ld2(row(dag, a)), y = ld2(row(dag, b));
+            if (!bv_eq(x, y)) return u_lt(x, y);
+        }
+        return a < b;
     }
+};
+
+__global__ __launch_bounds__(BV_BLOCK) void k_bv_lexmin(const uint4 *__restrict__ values, uint32_t n_models,
+                                                        const uint32_t *__restrict__ cons_off,
+                                                        const uint32_t *__restrict__ cons_dag,
+                                                        const uint32_t *__restrict__ obj_off,
+                                                        const uint32_t *__restrict__ obj_dag,
+                                                        uint32_t *__restrict__ best_model,
+                                                        uint32_t *__restrict__ best_values,
+                                                        uint32_t *__restrict__ cand_count) {
+    __shared__ uint32_t w_best[BV_BLOCK / 64u], w_cnt[BV_BLOCK / 64u];
+    const uint32_t q = blockIdx.x, tid = threadIdx.x;
+    const uint32_t c0 = cons_off[q], c1 = cons_off[q + 1], o0 = obj_off[q], o1 = obj_off[q + 1];
+    const BvMinQuery Q{values, obj_dag + o0, o1 - o0, n_models};
+    uint32_t best = BV_NO_MODEL, cnt = 0u;
+    for (uint32_t m = tid; m < n_models; m += BV_BLOCK) {      // ascending: a tie keeps the earlier model
+        uint32_t ok = 1u;
+        for (uint32_t k = c0; k < c1; ++k) ok &= Q.row(cons_dag[k], m)->x;
+        if (!(ok & 1u)) continue;
+        ++cnt;
+        if (Q.less(m, best)) best = m;
+    }
+    for (uint32_t off = 32u; off; off >>= 1) {                  // the wave's 64 lanes
+        const uint32_t other = (uint32_t)__shfl_xor((int)best, (int)off, 64);
+        cnt += (uint32_t)__shfl_xor((int)cnt, (int)off, 64);
+        if (Q.less(other, best)) best = other;
+    }
+    if ((tid & 63u) == 0u) { w_best[tid >> 6] = best; w_cnt[tid >> 6] = cnt; }
     __syncthreads();
-    const uint32_t tid = wave0 + __lane_id();
-    if (tid < d1 - d0) {
-        const uint32_t n = blk_cnt[tid], f = blk_first[tid];
-        if (n) {
-            atomicAdd(&sat_count[d0 + tid], n);
-            atomicMin(&first_sat[d0 + tid], f);
-        }
+    best = w_best[0];
+    cnt = w_cnt[0];
+    for (uint32_t w = 1; w < BV_BLOCK / 64u; ++w) {             // every thread: the same block result
+        if (Q.less(w_best[w], best)) best = w_best[w];
+        cnt += w_cnt[w];
+    }
+    if (tid == 0u) { best_model[q] = best; cand_count[q] = cnt; }
+    if (tid < Q.n_obj * 8u) {                                   // <= MG_MIN_OBJ * 8 = 64 limbs
+        const uint32_t j = tid >> 3, l = tid & 7u;
+        best_values[(o0 + j) * 8u + l] = best == BV_NO_MODEL ? 0xffffffffu :
+            reinterpret_cast<const uint32_t *>(Q.row(Q.obj[j], best))[l];
     }
 }
 
@@ -640,7 +495,7 @@ static void bv_free(BvState &s) {
     hipFree(s.insns); hipFree(s.prog_off); hipFree(s.tile_dag); hipFree(s.consts);
     hipFree(s.values); hipFree(s.first_sat); hipFree(s.sat_count);
     hipFree(s.tab_start); hipFree(s.tab_count); hipFree(s.tab_entries); hipFree(s.tab_default);
-    hipFree(s.sat_bits);
+    hipFree(s.sat_bits); hipFree(s.term_values); hipFree(s.min_buf);
     s = BvState{};
 }
 
@@ -881,20 +736,12 @@ static int bv_upload(BvState &s, const mg_dag_batch *dags, const mg_model_batch 
     return 0;
 }
 
-static int bv_run(BvState &s, uint32_t dag_first, uint32_t dag_count, hipStream_t st, std::string &msg) {
-    if (!s.n_dags) { msg = "mg_eval_run before mg_eval_upload"; return MG_ESTATE; }
-    if (dag_first + (uint64_t)dag_count > s.n_dags || dag_count == 0) { msg = "DAG range out of bounds"; return MG_EINVAL; }
-    const uint32_t dag_hi = dag_first + dag_count;
-    hipError_t e = hipMemsetAsync(s.first_sat + dag_first, 0xff, (size_t)dag_count * 4, st);
-    if (e == hipSuccess) e = hipMemsetAsync(s.sat_count + dag_first, 0, (size_t)dag_count * 4, st);
-    const uint32_t bit_words = (s.n_models + 63u) / 64u;
-    if (s.want_bits) {
-        const size_t need = (size_t)s.n_dags * bit_words;
-        if (bv_ensure(s.sat_bits, s.cap_bits, need)) { msg = "alloc sat bitmap"; return MG_ENOMEM; }
-        if (e == hipSuccess)
-            e = hipMemsetAsync(s.sat_bits + (size_t)dag_first * bit_words, 0, (size_t)dag_count * bit_words * 8, st);
-    }
-    if (e != hipSuccess) { msg = hipGetErrorString(e); return MG_EDEVICE; }
+// The launch shape of the interpreter kernels over DAGs [dag_first, dag_hi)
+struct BvGrid {
+    uint32_t t0, nt, tiles_pad, cpb;
+    size_t grid, lds;
+};
+static int bv_grid(const BvState &s, uint32_t dag_first, uint32_t dag_hi, BvGrid &g, std::string &msg) {
     // tiles covering [dag_first, dag_hi)
     const auto &t = s.h_tiles;
     uint32_t t0 = (uint32_t)(std::upper_bound(t.begin(), t.end(), dag_first) - t.begin()) - 1;
@@ -910,6 +757,28 @@ static int bv_run(BvState &s, uint32_t dag_first, uint32_t dag_count, hipStream_
     const uint32_t groups = (chunks + cpb - 1u) / cpb;
     const size_t grid = (size_t)tiles_pad * groups;
     if (grid > 0x7fffffffull) { msg = "grid too large"; return MG_EINVAL; }
+    g = BvGrid{t0, nt, tiles_pad, cpb, grid, (size_t)s.n_slots * 2 * BV_BLOCK * sizeof(uint4)};
+    return 0;
+}
+
+static int bv_run(BvState &s, uint32_t dag_first, uint32_t dag_count, hipStream_t st, std::string &msg) {
+    if (!s.n_dags) { msg = "mg_eval_run before mg_eval_upload"; return MG_ESTATE; }
+    if (dag_first + (uint64_t)dag_count > s.n_dags || dag_count == 0) { msg = "DAG range out of bounds"; return MG_EINVAL; }
+    const uint32_t dag_hi = dag_first + dag_count;
+    hipError_t e = hipMemsetAsync(s.first_sat + dag_first, 0xff, (size_t)dag_count * 4, st);
+    if (e == hipSuccess) e = hipMemsetAsync(s.sat_count + dag_first, 0, (size_t)dag_count * 4, st);
+    const uint32_t bit_words = (s.n_models + 63u) / 64u;
+    if (s.want_bits) {
+        const size_t need = (size_t)s.n_dags * bit_words;
+        if (bv_ensure(s.sat_bits, s.cap_bits, need)) { msg = "alloc sat bitmap"; return MG_ENOMEM; }
+        if (e == hipSuccess)
+            e = hipMemsetAsync(s.sat_bits + (size_t)dag_first * bit_words, 0, (size_t)dag_count * bit_words * 8, st);
+    }
+    if (e != hipSuccess) { msg = hipGetErrorString(e); return MG_EDEVICE; }
+    BvGrid g;
+    if (int rc = bv_grid(s, dag_first, dag_hi, g, msg)) return rc;
+    const uint32_t t0 = g.t0, nt = g.nt, tiles_pad = g.tiles_pad, cpb = g.cpb;
+    const size_t grid = g.grid;
     const size_t lds = (size_t)s.n_slots * 2 * BV_BLOCK * sizeof(uint4);
     static bool lds_attr = false;      // programs with more than 4 slots need > 64 KiB of LDS
     if (!lds_attr) {
@@ -942,5 +811,92 @@ static int bv_download(BvState &s, uint32_t *first_sat, uint32_t *sat_count, uin
         e = hipMemcpyAsync(sat_count, s.sat_count + dag_first, (size_t)dag_count * 4, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) { msg = hipGetErrorString(e); return MG_EDEVICE; }
+    return 0;
+}
+
+// k_bv_terms over every uploaded program: s.term_values[d][m] <- the value of
+// program d under model m.  The buffer is device-resident scratch; with 32-bit
+// offsets in the kernels it stays under 4 GiB.
+static int bv_terms(BvState &s, hipStream_t st, std::string &msg) {
+    if (!s.n_dags) { msg = "term evaluation before an upload"; return MG_ESTATE; }
+    if ((uint64_t)s.n_dags * s.n_models * 32u >= (1ull << 32)) {
+        msg = "term values over 4 GiB (programs x models x 32 bytes)";
+        return MG_EINVAL;
+    }
+    if (bv_ensure(s.term_values, s.cap_terms, (size_t)s.n_dags * s.n_models * 2)) { msg = "alloc term values"; return MG_ENOMEM; }
+    BvGrid g;
+    if (int rc = bv_grid(s, 0, s.n_dags, g, msg)) return rc;
+    static bool lds_attr = false;      // programs with more than 4 slots need > 64 KiB of LDS
+    if (!lds_attr) {
+        (void)hipFuncSetAttribute((const void *)k_bv_terms, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)(BV_MAX_SLOTS * 2 * BV_BLOCK * sizeof(uint4)));
+        lds_attr = true;
+    }
+    hipLaunchKernelGGL(k_bv_terms, dim3((unsigned)g.grid), dim3(BV_BLOCK), g.lds, st,
+                       s.insns, s.prog_off, s.tile_dag,
+                       s.consts, s.values, s.n_models, BvTables{s.tab_start, s.tab_count, s.tab_entries, s.tab_default},
+                       s.n_slots, g.t0, g.nt, g.tiles_pad, 0u, s.n_dags, s.tile_cap, g.cpb, s.term_values);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { msg = std::string("k_bv_terms launch: ") + hipGetErrorString(e); return MG_EDEVICE; }
+    return 0;
+}
+
+// The query lists of an mg_min_batch, checked against a batch of n_dags programs
+// (before anything is uploaded or launched).
+static int bv_min_validate(const mg_min_batch *q, uint32_t n_dags, std::string &msg) {
+    if (!q->n_queries || !q->cons_off || !q->obj_off) { msg = "empty minimisation batch"; return MG_EINVAL; }
+    for (int which = 0; which < 2; ++which) {
+        const uint32_t *off = which ? q->obj_off : q->cons_off, *dag = which ? q->obj_dag : q->cons_dag;
+        const char *what = which ? "objective" : "constraint";
+        if (off[0] != 0u) { msg = std::string(what) + " offsets do not start at 0"; return MG_EINVAL; }
+        for (uint32_t k = 0; k < q->n_queries; ++k) {
+            if (off[k + 1] < off[k]) { msg = std::string(what) + " offsets decrease at query " + std::to_string(k); return MG_EINVAL; }
+            if (which && off[k + 1] - off[k] > MG_MIN_OBJ) {
+                msg = "query " + std::to_string(k) + " has more than " + std::to_string(MG_MIN_OBJ) + " objectives";
+                return MG_EINVAL;
+            }
+        }
+        const uint32_t total = off[q->n_queries];
+        if (total && !dag) { msg = std::string(what) + " list missing"; return MG_EINVAL; }
+        if ((uint64_t)total * 8u >= (1ull << 28)) { msg = std::string(what) + " list too long"; return MG_EINVAL; }
+        for (uint32_t k = 0; k < total; ++k)
+            if (dag[k] >= n_dags) {
+                msg = std::string(what) + " DAG index " + std::to_string(dag[k]) + " out of range (" +
+                      std::to_string(n_dags) + " programs)";
+                return MG_EINVAL;
+            }
+    }
+    return 0;
+}
+
+// k_bv_lexmin over s.term_values (bv_terms first, same stream).  min_buf holds
+// the lists [cons_off | obj_off | cons_dag | obj_dag] and then the results
+// [best_model | cand_count | best_values].
+static int bv_lexmin(BvState &s, const mg_min_batch *q, uint32_t *best_model, uint32_t *best_values,
+                     uint32_t *cand_count, hipStream_t st, hipEvent_t done, std::string &msg) {
+    const uint32_t nq = q->n_queries, nc = q->cons_off[nq], no = q->obj_off[nq];
+    const size_t in_words = 2 * ((size_t)nq + 1) + nc + no, out_words = 2 * (size_t)nq + (size_t)no * 8;
+    if (bv_ensure(s.min_buf, s.cap_min, in_words + out_words)) { msg = "alloc minimisation lists"; return MG_ENOMEM; }
+    s.h_min.clear();
+    s.h_min.insert(s.h_min.end(), q->cons_off, q->cons_off + nq + 1);
+    s.h_min.insert(s.h_min.end(), q->obj_off, q->obj_off + nq + 1);
+    if (nc) s.h_min.insert(s.h_min.end(), q->cons_dag, q->cons_dag + nc);
+    if (no) s.h_min.insert(s.h_min.end(), q->obj_dag, q->obj_dag + no);
+    hipError_t e = hipMemcpyAsync(s.min_buf, s.h_min.data(), in_words * 4, hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) { msg = hipGetErrorString(e); return MG_EDEVICE; }
+    uint32_t *d_cons_off = s.min_buf, *d_obj_off = d_cons_off + nq + 1, *d_cons = d_obj_off + nq + 1,
+             *d_obj = d_cons + nc, *d_best = d_obj + no, *d_cnt = d_best + nq, *d_vals = d_cnt + nq;
+    hipLaunchKernelGGL(k_bv_lexmin, dim3(nq), dim3(BV_BLOCK), 0, st, s.term_values, s.n_models, d_cons_off, d_cons,
+                       d_obj_off, d_obj, d_best, d_vals, d_cnt);
+    e = hipGetLastError();
+    if (e != hipSuccess) { msg = std::string("k_bv_lexmin launch: ") + hipGetErrorString(e); return MG_EDEVICE; }
+    if (done && (e = hipEventRecord(done, st)) != hipSuccess) { msg = hipGetErrorString(e); return MG_EDEVICE; }
+    s.h_min.assign(out_words, 0u);
+    e = hipMemcpyAsync(s.h_min.data(), d_best, out_words * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) { msg = hipGetErrorString(e); return MG_EDEVICE; }
+    if (best_model) std::memcpy(best_model, s.h_min.data(), (size_t)nq * 4);
+    if (cand_count) std::memcpy(cand_count, s.h_min.data() + nq, (size_t)nq * 4);
+    if (best_values && no) std::memcpy(best_values, s.h_min.data() + 2 * (size_t)nq, (size_t)no * 32);
     return 0;
 }

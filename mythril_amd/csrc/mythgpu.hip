@@ -1553,6 +1553,44 @@ extern "C" int mg_eval(mg_ctx *ctx, const mg_dag_batch *dags, const mg_model_bat
     return mg_eval_download(ctx, first_sat, sat_count, 0, dags->n_dags);
 }
 
+extern "C" int mg_eval_terms(mg_ctx *ctx, const mg_dag_batch *dags, const mg_model_batch *models, uint32_t *values,
+                             float *kernel_ms) {
+    if (!ctx || !dags || !models || !values) return MG_EINVAL;
+    if ((uint64_t)dags->n_dags * models->n_models * 32u >= (1ull << 32))
+        return set_err(ctx, MG_EINVAL, "term values over 4 GiB (programs x models x 32 bytes)");
+    int rc;
+    if ((rc = mg_eval_upload(ctx, dags, models))) return rc;
+    std::string msg;
+    if (kernel_ms) HIPX(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    if ((rc = bv_terms(ctx->bv, ctx->stream, msg))) return set_err(ctx, rc, "%s", msg.c_str());
+    if (kernel_ms) HIPX(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+    HIPX(ctx, hipMemcpyAsync(values, ctx->bv.term_values, (size_t)dags->n_dags * models->n_models * 32,
+                             hipMemcpyDeviceToHost, ctx->stream));
+    HIPX(ctx, hipStreamSynchronize(ctx->stream));
+    if (kernel_ms) HIPX(ctx, hipEventElapsedTime(kernel_ms, ctx->ev0, ctx->ev1));
+    return MG_OK;
+}
+
+extern "C" int mg_eval_min(mg_ctx *ctx, const mg_dag_batch *dags, const mg_model_batch *models,
+                           const mg_min_batch *queries, uint32_t *best_model, uint32_t *best_values,
+                           uint32_t *cand_count, float *kernel_ms) {
+    if (!ctx || !dags || !models || !queries) return MG_EINVAL;
+    std::string msg;
+    int rc;
+    // everything the kernels index by is checked before the first upload or launch
+    if ((rc = bv_min_validate(queries, dags->n_dags, msg))) return set_err(ctx, rc, "mg_eval_min: %s", msg.c_str());
+    if ((uint64_t)dags->n_dags * models->n_models * 32u >= (1ull << 32))
+        return set_err(ctx, MG_EINVAL, "term values over 4 GiB (programs x models x 32 bytes)");
+    if ((rc = mg_eval_upload(ctx, dags, models))) return rc;
+    if (kernel_ms) HIPX(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    if ((rc = bv_terms(ctx->bv, ctx->stream, msg))) return set_err(ctx, rc, "%s", msg.c_str());
+    if ((rc = bv_lexmin(ctx->bv, queries, best_model, best_values, cand_count, ctx->stream,
+                        kernel_ms ? ctx->ev1 : nullptr, msg)))
+        return set_err(ctx, rc, "%s", msg.c_str());
+    if (kernel_ms) HIPX(ctx, hipEventElapsedTime(kernel_ms, ctx->ev0, ctx->ev1));
+    return MG_OK;
+}
+
 // ------------------------------------------------------------ conjunct compiler
 // mg_cc_*: kernel 2's program compiler on the host, over a growing native node
 // table (csrc/cc.h; the passes of mythril_amd/smt/flatten.py).

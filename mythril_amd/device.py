@@ -272,3 +272,42 @@ class GpuDevice:
         ms = self.eval_run()
         fs, sc = self.eval_download()
         return fs, sc, ms
+
+    def eval_terms(self, program, models):
+        """mg_eval_terms: (values uint32[n_dags, n_models, 8], ms) -- the value of
+        every program's final accumulator under every model, little-endian limbs."""
+        dags, mods = program.c_struct(), models.c_struct()
+        out = np.zeros((program.n_dags, models.n_models, 8), dtype=np.uint32)
+        ms = ctypes.c_float()
+        self._check(self.lib.mg_eval_terms(self.ctx, ctypes.byref(dags), ctypes.byref(mods), out.ctypes.data,
+                                           ctypes.byref(ms)), "mg_eval_terms")
+        return out, ms.value
+
+    def eval_min(self, program, models, cons, objs):
+        """mg_eval_min.  cons[q] / objs[q]: the program indices that must hold /
+        that are minimised (most significant first) for query q.  Returns
+        (best_model uint32[n_queries], best_values: per query uint32[len(objs[q]), 8],
+        cand_count uint32[n_queries], ms); best_model 0xFFFFFFFF = no candidate."""
+        if len(cons) != len(objs):
+            raise ValueError("eval_min: one constraint list and one objective list per query")
+        nq = len(cons)
+
+        def lists(xs):
+            off = np.zeros(nq + 1, dtype=np.uint32)
+            off[1:] = np.cumsum([len(x) for x in xs], dtype=np.int64)
+            flat = np.array([int(i) for x in xs for i in x] or [0], dtype=np.uint32)
+            return off, flat
+
+        c_off, c_dag = lists(cons)
+        o_off, o_dag = lists(objs)
+        dags, mods = program.c_struct(), models.c_struct()
+        batch = native.MgMinBatch(nq, 0, c_off.ctypes.data, c_dag.ctypes.data, o_off.ctypes.data, o_dag.ctypes.data)
+        best = np.zeros(max(nq, 1), dtype=np.uint32)
+        count = np.zeros(max(nq, 1), dtype=np.uint32)
+        vals = np.zeros((max(int(o_off[-1]), 1), 8), dtype=np.uint32)
+        ms = ctypes.c_float()
+        self._check(self.lib.mg_eval_min(self.ctx, ctypes.byref(dags), ctypes.byref(mods), ctypes.byref(batch),
+                                         best.ctypes.data, vals.ctypes.data, count.ctypes.data, ctypes.byref(ms)),
+                    "mg_eval_min")
+        per_query = [vals[int(o_off[q]):int(o_off[q + 1])] for q in range(nq)]
+        return best[:nq], per_query, count[:nq], ms.value

@@ -102,6 +102,12 @@ class MgModelBatch(ctypes.Structure):
                 ("tab_default", ctypes.c_void_p)]
 
 
+class MgMinBatch(ctypes.Structure):
+    _fields_ = [("n_queries", ctypes.c_uint32), ("_pad", ctypes.c_uint32),
+                ("cons_off", ctypes.c_void_p), ("cons_dag", ctypes.c_void_p),
+                ("obj_off", ctypes.c_void_p), ("obj_dag", ctypes.c_void_p)]
+
+
 # every symbol include/mythgpu.h declares: name -> (restype, argtypes)
 _P, _U32, _U64, _I = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int
 _PU32 = ctypes.POINTER(ctypes.c_uint32)
@@ -140,6 +146,10 @@ SIGNATURES = {
     "mg_event_counts": (_I, [_P, _P, _P, _U32, _U32]),
     "mg_eval": (_I, [_P, ctypes.POINTER(MgDagBatch), ctypes.POINTER(MgModelBatch), _P, _P,
                      ctypes.POINTER(ctypes.c_float)]),
+    "mg_eval_terms": (_I, [_P, ctypes.POINTER(MgDagBatch), ctypes.POINTER(MgModelBatch), _P,
+                           ctypes.POINTER(ctypes.c_float)]),
+    "mg_eval_min": (_I, [_P, ctypes.POINTER(MgDagBatch), ctypes.POINTER(MgModelBatch),
+                         ctypes.POINTER(MgMinBatch), _P, _P, _P, ctypes.POINTER(ctypes.c_float)]),
     "mg_eval_upload": (_I, [_P, ctypes.POINTER(MgDagBatch), ctypes.POINTER(MgModelBatch)]),
     "mg_eval_run": (_I, [_P, _U32, _U32, ctypes.POINTER(ctypes.c_float)]),
     "mg_eval_download": (_I, [_P, _P, _P, _U32, _U32]),

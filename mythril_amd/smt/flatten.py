@@ -109,6 +109,24 @@ class PyCompiler:
         # arrays / functions / wide values -> 256-bit ops + table lookups (lower.py)
         self.lowering = Lowering()
         self.table_index: Dict[str, int] = {}
+        # first-seen order of the nodes (_number): breaks ties between operand
+        # subtrees of equal size the way the native compiler's node ids do
+        self._num: Dict[Node, int] = {}
+
+    def _number(self, root: Node) -> None:
+        """Number the nodes new to this compiler in the order NativeCompiler
+        registers them (post-order, the last operand's subtree first)."""
+        num = self._num
+        stack = [(root, False)]
+        while stack:
+            x, ready = stack.pop()
+            if x in num:
+                continue
+            if not ready:
+                stack.append((x, True))
+                stack.extend((c, False) for c in x.args if c not in num)
+                continue
+            num[x] = len(num)
 
     # -- leaves ---------------------------------------------------------------
     def _leaf_ref(self, n: Node) -> int:
@@ -129,16 +147,23 @@ class PyCompiler:
     # -- scheduling -----------------------------------------------------------
     @staticmethod
     def _sizes(root: Node, size: Dict[Node, int]):
-        order, st = [], [root]
+        """Tree size of every internal node (a shared operand counted per use),
+        children before parents; saturating as cc.h's 64-bit count does."""
+        st = [(root, False)]
         while st:
-            x = st.pop()
+            x, ready = st.pop()
             if x in size or x.op in ("const", "var"):
                 continue
-            size[x] = 0
-            order.append(x)
-            st.extend(x.args)
-        for x in reversed(order):
-            size[x] = 1 + sum(size.get(c, 0) for c in x.args)
+            if not ready:
+                st.append((x, True))
+                st.extend((c, False) for c in x.args)
+                continue
+            s = 1
+            for c in x.args:
+                s += size.get(c, 0)
+                if s >> 64:
+                    s = (1 << 64) - 2
+            size[x] = s
 
     def _emit(self, n: Node, virts: List[_Virt], vid: Dict[Node, int], size: Dict[Node, int]):
         """Post-order emission of n's subtree; operands with bigger subtrees first so
@@ -152,8 +177,9 @@ class PyCompiler:
                 raise Unsupported("bit-vector wider than 256 bits")
             if not ready:
                 stack.append((x, True))
-                kids = sorted((c for c in set(x.args) if c not in vid and c.op not in ("const", "var")),
-                              key=lambda c: size.get(c, 0))
+                # ascending size, ties by first-seen order (cc.h: lower node id first)
+                kids = sorted((c for c in dict.fromkeys(x.args) if c not in vid and c.op not in ("const", "var")),
+                              key=lambda c: (size.get(c, 0), self._num[c]))
                 for c in kids:            # pushed smallest-first => computed largest-first
                     stack.append((c, False))
                 continue
@@ -225,7 +251,10 @@ class PyCompiler:
 
     # -- slots + encoding -----------------------------------------------------
     def compile(self, root: Node) -> np.ndarray:
-        root = _fold_select(self.lowering.lower(root))
+        low = self.lowering.lower(root)
+        self._number(low)
+        root = _fold_select(low)
+        self._number(root)                # the nodes the fold rebuilt, in the order it made them
         virts = self._schedule(root)
         n = len(virts)
         uses: Dict[int, List[Tuple[int, int]]] = {}
@@ -428,6 +457,27 @@ def compile_sets(sets: Sequence[Sequence], compiler: PyCompiler = None) -> Tuple
         tables[t] = c.lowering.tables[name]
     return ProgramBatch(insns, off, consts, max(c.max_slots, 1), names, list(c.var_widths),
                         tables), kept
+
+
+def compile_terms(terms: Sequence, compiler: PyCompiler = None) -> Tuple[ProgramBatch, List[int]]:
+    """Compile terms (BitVec / Bool / Node roots of width <= 256) into one
+    ProgramBatch whose programs leave the term's VALUE in the accumulator (a
+    lone variable or constant is one ``copy``): the programs of mg_eval_terms,
+    and the objectives of mg_eval_min.  Returns the batch and the indices of the
+    terms it contains; wider roots, and terms the device does not evaluate, are
+    left out."""
+    c = compiler or Compiler()
+    progs, kept = [], []
+    for k, t in enumerate(terms):
+        raw = t.raw if hasattr(t, "raw") else t
+        try:
+            if raw.width > 256:
+                raise Unsupported("term wider than 256 bits")
+            progs.append(c.compile(raw))
+            kept.append(k)
+        except Unsupported:
+            continue
+    return batch_from(c, progs), kept
 
 
 def batch_from(c: "PyCompiler", progs: List[np.ndarray]) -> ProgramBatch:

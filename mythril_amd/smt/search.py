@@ -26,19 +26,23 @@ Where a model comes from, in order:
    best are repaired again for a few rounds.
 3. minimised terms (get_transaction_sequence's calldata sizes and call values,
    analysis/solver.py:219-259) are lowered afterwards by a batched descent --
-   a local minimum, not z3 Optimize's global one.
+   a local minimum, not z3 Optimize's global one.  With ``global_min`` (the
+   MYTHSMT_GLOBAL_MIN=1 knob, off by default) the lexicographic optimum
+   follows: kernel 2 picks the best candidate model, the exact procedure's
+   minimiser decides under its bound, kernel 2 re-checks (``_global_min``).
 
 A model is returned only when kernel 2 found it satisfying every conjunct of
 the query; the host does not decide satisfaction anywhere.
 """
 from __future__ import annotations
 
+import os
 from collections import OrderedDict
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .expr import TRUE, Node
+from .expr import TRUE, Node, _fold, const
 from .program import ArrayInterp, FuncInterp, PoolColumns
 from .semantics import apply_op
 from .refute import refutes
@@ -573,8 +577,11 @@ class SatSearchBackend:
 
     def __init__(self, cache, search: bool = True, rounds: int = 12, beam: int = 6,
                  max_candidates: int = 4096, patience: int = 3, seed: int = 0x5EA5C4,
-                 exact=None, exact_ms: int = 60000):
+                 exact=None, exact_ms: int = 60000, global_min: Optional[bool] = None):
         self.cache = cache
+        # the lexicographic optimum of the minimised terms instead of _minimise's
+        # local one (_global_min); None: the MYTHSMT_GLOBAL_MIN=1 knob, default off
+        self.global_min = os.environ.get("MYTHSMT_GLOBAL_MIN") == "1" if global_min is None else bool(global_min)
         self.search = search
         self.exact = exact
         self.exact_ms = exact_ms
@@ -591,7 +598,8 @@ class SatSearchBackend:
         self._start_cols: Optional[tuple] = None      # (the starting pool's assignments, their PoolColumns)
         self.stats: Dict[str, int] = {"calls": 0, "refuted": 0, "seed": 0, "search": 0, "unknown": 0,
                                       "candidates": 0, "launches": 0, "minimised": 0,
-                                      "exact_sat": 0, "exact_unsat": 0, "exact_timeout": 0}
+                                      "exact_sat": 0, "exact_unsat": 0, "exact_timeout": 0,
+                                      "min_device": 0, "min_exact": 0, "min_improved": 0, "min_unproved": 0}
 
     def __call__(self, constraints, minimize, maximize, timeout):
         self.stats["calls"] += 1
@@ -607,12 +615,14 @@ class SatSearchBackend:
             if model is not None:
                 self.stats["search"] += 1
         if model is None and self.exact is not None:
-            return self._decide(key, minimize, timeout)
-        if model is None:
+            model = self._decide(key, minimize, timeout)
+        elif model is None:
             self.stats["unknown"] += 1
             raise SolverBackendMissing("SAT-only backend: no candidate model satisfies the query (unknown)")
-        if minimize:
+        elif minimize:
             model = self._minimise(key, model, minimize)
+        if minimize and self.global_min:
+            model = self._global_min(key, model, minimize, timeout)
         return model
 
     def _decide(self, key: Node, minimize, timeout) -> Model:
@@ -646,6 +656,68 @@ class SatSearchBackend:
                 self.stats["exact_timeout"] += 1
                 raise SolverTimeOutException
         raise RuntimeError("the exact procedure's model does not satisfy the query on kernel 2")
+
+    def _global_min(self, key: Node, model: Model, minimize, timeout) -> Model:
+        """The lexicographic optimum of the minimised terms (z3 Optimize with
+        minimize() per term in priority order, support/model.py:56-82), from the
+        model the cheaper answers produced.  Kernel 2 picks the incumbent: the
+        lexicographically smallest satisfying model among that one, the LRU's and
+        the completed seeds (ModelCache.lex_min).  An all-zero tuple is minimal;
+        otherwise the exact procedure's minimiser decides the query under the
+        incumbent's first objective as a bound (a unit: it folds), kernel 2
+        re-checks its assignment and computes its tuple, and the smaller of the
+        two is returned.  What the exact procedure leaves open keeps the
+        incumbent and is counted in stats["min_unproved"].  Neither satisfaction
+        nor an objective's value is evaluated on the host."""
+        conj = [c for c in _conjuncts(key) if c is not TRUE]
+        live = [c for c in conj if c.op != "const"]
+        mins = [m.raw if hasattr(m, "raw") else m for m in minimize]
+        lru = [m for m in reversed(self.cache.model_cache.lru_cache.keys()) if isinstance(m, Model) and m is not model]
+        others = lru + list(self.cache._seed_models() or [])
+        pool = [model] + [_model(self._completed(m.raw[-1].assignment)) for m in others]
+        idx, best, _ = self.cache.lex_min(live, mins, pool)
+        self.stats["min_device"] += 1
+        if idx is False:
+            self.stats["min_unproved"] += 1        # no kernel-2 program: today's answer stands, unproved
+            return model
+        if idx is None:
+            raise RuntimeError("the answered model is not a candidate of its own query on kernel 2")
+        incumbent = pool[idx]
+        if not any(best):
+            return incumbent
+        if self.exact is None:
+            self.stats["min_unproved"] += 1
+            return incumbent
+        bound = _fold("bvule", 1, (mins[0], const(best[0], mins[0].width)))
+        bounded = conj + ([bound] if bound is not TRUE else [])
+        max_ms = max(1, min(int(self.exact_ms), int(timeout))) if timeout else max(int(self.exact_ms), 1)
+        fresh = False
+        for attempt in range(2):
+            try:
+                st, assign = self.exact.check(bounded, mins, max_ms=max_ms, fresh=fresh)
+            except ValueError:                     # exact.Unsupported: a term it does not blast
+                st, assign = "unknown", None
+            self.stats["min_exact"] += 1
+            if st == "unsat":
+                raise RuntimeError("the exact procedure refutes a query its incumbent model satisfies on kernel 2")
+            if st == "unknown":
+                self.stats["min_unproved"] += 1
+                return incumbent
+            found = _model(assign)
+            jdx, got, _ = self.cache.lex_min(live, mins, [found])
+            self.stats["min_device"] += 1
+            if jdx is False:
+                self.stats["min_unproved"] += 1
+                return incumbent
+            if jdx is not None:
+                if tuple(got) < tuple(best):
+                    self.stats["min_improved"] += 1
+                    return found
+                return incumbent
+            # kernel 2 rejects the assignment: decided once more alone, as _decide does
+            self.stats["exact_recheck"] = self.stats.get("exact_recheck", 0) + 1
+            fresh = True
+        raise RuntimeError("the exact procedure's minimal model does not satisfy the query on kernel 2")
 
     def _holds(self, live, assign) -> bool:
         counts, hit = self._score(live, [assign])

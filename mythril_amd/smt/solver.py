@@ -644,6 +644,71 @@ class ModelCache:
                     rows[c] = ~r & valid
         return rows
 
+    # -- lexicographic minimum over a pool ----------------------------------------
+    MIN_OBJECTIVES = 8          # MG_MIN_OBJ: objectives one mg_eval_min query takes
+
+    def _program(self, node: Node):
+        """The node's kernel-2 program from the persistent compiler (its value in
+        the final accumulator: a truth value for a conjunct, the term's value for
+        an objective), or None when the device does not evaluate it."""
+        pr = self._progs.get(node, _MISSING)
+        if pr is _MISSING:
+            if self._compiler is None:
+                self._compiler = Compiler()
+            try:
+                if node.width > 256:
+                    raise Unsupported("term wider than 256 bits")
+                pr = self._compiler.compile(node)
+            except Unsupported:
+                pr = None
+            self._progs[node] = pr
+        return pr
+
+    def lex_min(self, conjuncts: Sequence[Node], objectives: Sequence[Node], pool: List, columns=None):
+        """(index, objective values, candidate count) of the pool model that
+        satisfies every conjunct with the lexicographically smallest objective
+        tuple (unsigned values, first objective most significant, ties to the
+        earliest model), chosen on the device in ONE mg_eval_min launch: one
+        program per conjunct and per objective, compiled once per cache.  The
+        index is None when no pool model satisfies the conjuncts, and False (as
+        _score's) when a conjunct or objective has no kernel-2 program or there
+        are more than MIN_OBJECTIVES objectives: nothing can then be reported."""
+        if not pool:
+            return None, [], 0
+        cons = [c for c in conjuncts if c.op != "const"]
+        if any(c.op == "const" and not c.param for c in conjuncts):
+            return None, [], 0
+        if len(objectives) > self.MIN_OBJECTIVES:
+            return False, [], 0
+        index: "OrderedDict[Node, int]" = OrderedDict()
+        progs = []
+        for n in list(cons) + list(objectives):
+            if n in index:
+                continue
+            pr = self._program(n)
+            if pr is None:
+                return False, [], 0
+            index[n] = len(progs)
+            progs.append(pr)
+        if not progs:
+            return 0, [], len(pool)              # nothing to satisfy, nothing to minimise
+        prog = batch_from(self._compiler, progs)
+        if columns is not None:
+            mp = columns.pool(prog.var_names, prog.var_widths, prog.tables)
+        else:
+            if not self._seed_tailed(pool):
+                prog = compact_vars(prog)
+            mp = self._pool(pool, prog)
+        best, vals, count, ms = self.device.eval_min(prog, mp, [[index[c] for c in cons]],
+                                                     [[index[t] for t in objectives]])
+        self.part_evals += len(progs) * len(pool)
+        self.device_ms += float(ms or 0.0)
+        self.launches += 1
+        if int(best[0]) == NO_MODEL:
+            return None, [], 0
+        values = [int.from_bytes(np.ascontiguousarray(row, dtype="<u4").tobytes(), "little") for row in vals[0]]
+        return int(best[0]), values, int(count[0])
+
     # -- witness seeds and prefetched groups ------------------------------------
     def _seed_models(self) -> List:
         if self.seed_source is not None:
