@@ -114,7 +114,7 @@ extern "C" {
 #define MG_ESC_RECORD   6u   /* function-manager record log would grow past rec_cap */
 #define MG_ESC_SYMBOLIC 7u   /* symbolic operand the device has no symbolic semantics for */
 #define MG_ESC_ARENA    8u   /* the lane's expression arena / constant table is full */
-#define MG_ESC_TAINT    9u   /* the lane's annotation atoms (64) or object table are full */
+#define MG_ESC_TAINT    9u   /* the lane's annotation atoms (MG_TAINT_MAX_ATOMS) or object table are full */
 
 /* Function-manager records: what the reference registers with its global
  * function managers while a path runs, logged per lane in execution order so
@@ -166,6 +166,7 @@ extern "C" {
  *                  length's arena node.  Precedes the SHA3's MG_REC_SYMKECCAK.      */
 #define MG_REC_SYMLEN   8u
 #define MG_REC_HEADER   11u  /* kind, len, step, 8 result limbs                */
+#define MG_REC_ANNOT_WORDS (MG_REC_HEADER + 11u)  /* an MG_REC_ANNOT record: stack[-2], pc, opcode, fent */
 
 /* lane flags */
 #define MG_LANE_STATIC    1u  /* environment.static (WriteProtection)          */
@@ -192,8 +193,6 @@ extern "C" {
                                  escape; without it they push 0 / pop only, as the
                                  reference does with last_return_data None
                                  (instructions.py:1314-1370)                       */
-
-/* environment words, per lane */
 #define MG_LANE_SYMBAL 32768u /* symbolic lane whose active account's balance is
                                  symbolic: SELFBALANCE pushes an MG_SYM_ENV node
                                  (w = MG_ENV_SELFBALANCE, instructions.py:968-976) */
@@ -201,11 +200,13 @@ extern "C" {
                                  size (a host CALL's returndatasize variable):
                                  RETURNDATASIZE pushes an MG_SYM_ENV node
                                  (w = MG_ENV_RETURNDATASIZE, instructions.py:1359-1370) */
-#define MG_LANE_SYMBLOCK 262144u /* symbolic lane whose environment's block_number and chainid are
-                                    symbolic: NUMBER / CHAINID push MG_SYM_ENV nodes          */
 #define MG_LANE_BALANCE 131072u /* symbolic lane of a LaserEVM with no dynamic loader: BALANCE
                                    pushes an MG_SYM_BALANCE node (the world state's accounts
                                    cannot change inside a device run)                    */
+#define MG_LANE_SYMBLOCK 262144u /* symbolic lane whose environment's block_number and chainid are
+                                    symbolic: NUMBER / CHAINID push MG_SYM_ENV nodes          */
+
+/* environment words, per lane */
 #define MG_ENV_ADDRESS   0
 #define MG_ENV_CALLER    1
 #define MG_ENV_ORIGIN    2
@@ -406,7 +407,11 @@ int         mg_sym_download(mg_ctx *ctx, mg_sym_soa *host, uint32_t first, uint3
                                     word is symbolic (yield then)                              */
 #define MG_TAINT_IFLANE     (1u << 24)  /* yield when the lane's tflags bit 1 is set (a state
                                     annotation the host found at pack)                          */
+#define MG_TAINT_FIELD_BITS  4   /* width of each operand field above (PRE, SINK, YIELD, DEFER, IFSYM) */
+#define MG_TAINT_FIELD(action, shift) (((action) >> (shift)) & ((1u << MG_TAINT_FIELD_BITS) - 1u))
+#define MG_TAINT_CDSIZE      6u  /* handle of the symbolic calldata-size object                */
 #define MG_TAINT_OBJ0        7u  /* first object-table handle                                  */
+#define MG_TAINT_MAX_ATOMS  64u  /* atoms per lane: one bit each of an annotation mask         */
 
 /* Host image of the taint planes of lanes [first, first + n), lane-major. */
 typedef struct mg_taint_soa {
@@ -553,7 +558,47 @@ int         mg_event_counts(mg_ctx *ctx, uint32_t *sha3_count, uint32_t *exp_cou
  * accumulator in operand B or C is refused with MG_EINVAL, and so is one
  * with any of bits 22..31 of the first word set (the library's own fused
  * forms use them: it rewrites common instruction pairs and chains into
- * superinstructions at upload, bit-identical results; MG_BV_FUSE=0 disables). */
+ * superinstructions at upload, bit-identical results; MG_BV_FUSE=0 disables).
+ *
+ * The opcodes, X(C name, name in the host's expression layer).  The result lands
+ * in the accumulator; A, B, C = the operands of words 1..3.                   */
+#define MG_BV_OP_LIST(X) \
+    X(COPY, "copy")               /* acc = A */ \
+    X(ADD, "bvadd") X(SUB, "bvsub") X(MUL, "bvmul") X(UDIV, "bvudiv") X(UREM, "bvurem") \
+    X(SDIV, "bvsdiv") X(SREM, "bvsrem") X(SMOD, "bvsmod") \
+    X(AND, "bvand") X(OR, "bvor") X(XOR, "bvxor") X(NOT, "bvnot") X(NEG, "bvneg") \
+    X(SHL, "bvshl") X(LSHR, "bvlshr") X(ASHR, "bvashr") \
+    X(EQ, "eq") X(ULT, "bvult") X(ULE, "bvule") X(UGT, "bvugt") X(UGE, "bvuge") \
+    X(SLT, "bvslt") X(SLE, "bvsle") X(SGT, "bvsgt") X(SGE, "bvsge")   /* w3 = operand width */ \
+    X(BAND, "and") X(BOR, "or") X(BXOR, "xor") X(BNOT, "not") X(BIMPLIES, "implies") \
+    X(ITE, "ite")                 /* A cond, B then, C else */ \
+    X(EXTRACT, "extract")         /* A, w2 = lo */ \
+    X(CONCAT, "concat")           /* A high, B low, w3 = width of B */ \
+    X(ZEXT, "zero_extend")        /* A (value already masked) */ \
+    X(SEXT, "sign_extend")        /* A, w2 = source width */ \
+    X(ADD_NOOVF_U, "bvadd_noovfl_u")   /* bvadd_noovfl unsigned; w3 = operand width */ \
+    X(MUL_NOOVF_U, "bvumul_noovfl")    /* bvumul_noovfl;        w3 = operand width */ \
+    X(SUB_NOUDF_U, "bvsub_noudfl_u")   /* BVSubNoUnderflow unsigned: b <= a */ \
+    X(NE, "distinct")             /* w3 = operand width */ \
+    X(TAB, "tab")                 /* A = key k0, B = key k1, w3 = table | part << MG_BV_TAB_PART_SHIFT | \
+                                     lo << MG_BV_TAB_LO_SHIFT: bits [256 part + lo, +width) of the model's \
+                                     array / function interpretation at (k0, k1), else its default */ \
+    X(UMIN, "bvumin") X(UMAX, "bvumax")   /* ite(cmp(A, B), A, B) folded by the compiler */ \
+    X(SMIN, "bvsmin") X(SMAX, "bvsmax")   /* signed at `width` */ \
+    X(RSUB, "bvrsub")             /* B - A           (operand-swapped forms: the accumulator is only */ \
+    X(RCONCAT, "rconcat")         /* A low, B high,   ever operand A; w3 = width of A) */
+#define MG_BV_ENUM_(name, host) MG_BV_##name,
+enum { MG_BV_OP_LIST(MG_BV_ENUM_) MG_BV_NUM_OPS };   /* MG_BV_COPY = 0, ... */
+#undef MG_BV_ENUM_
+#define MG_BV_REF_ACC   0u   /* operand reference kinds */
+#define MG_BV_REF_SLOT  1u
+#define MG_BV_REF_VAR   2u
+#define MG_BV_REF_CONST 3u
+#define MG_BV_MAX_SLOTS  16u    /* the 4-bit slot field                          */
+#define MG_BV_TILE_INSNS 2048u  /* longest program, in instructions              */
+#define MG_BV_TAB_INDEX_MASK 0xfffffu   /* MG_BV_TAB's immediate: table index,   */
+#define MG_BV_TAB_PART_SHIFT 20         /* 256-bit half of the 512-bit value,    */
+#define MG_BV_TAB_LO_SHIFT   21         /* low bit within it                     */
 typedef struct mg_dag_batch {
     uint32_t n_dags;
     uint32_t n_slots;       /* register slots a program may use (<= 16)       */
@@ -571,7 +616,7 @@ typedef struct mg_dag_batch {
  *
  * Tables are the models' interpretations of symbolic arrays (storage,
  * calldata, balances: array.py) and uninterpreted functions (keccak256_N and
- * its inverse, Power: function.py), looked up by the program op BV_TAB.  For
+ * its inverse, Power: function.py), looked up by the program op MG_BV_TAB.  For
  * table t and model m, entries [tab_start[t][m], + tab_count[t][m]) of
  * tab_entries hold (key k0: 8 limbs, key k1: 8 limbs, value: 16 limbs, i.e. up
  * to 512 bits); a key not listed takes tab_default[t][m] (array default /
@@ -589,8 +634,9 @@ typedef struct mg_model_batch {
 } mg_model_batch;
 
 /* first_sat_model[d] = smallest model index m (MRU order) whose evaluation of
- * DAG d is true, UINT32_MAX if none; sat_count[d] = number of satisfying
+ * DAG d is true, MG_BV_NO_MODEL if none; sat_count[d] = number of satisfying
  * models (may be NULL).                                                      */
+#define MG_BV_NO_MODEL 0xffffffffu
 int         mg_eval(mg_ctx *ctx, const mg_dag_batch *dags, const mg_model_batch *models,
                     uint32_t *first_sat_model, uint32_t *sat_count, float *kernel_ms);
 
@@ -626,7 +672,7 @@ int         mg_eval_terms(mg_ctx *ctx, const mg_dag_batch *dags, const mg_model_
  * the candidate with the smallest objective tuple -- each objective an unsigned
  * 256-bit number, the tuple compared in list order, ties to the smallest model
  * index.  Constraint and objective programs are DAGs of the one `dags` batch.
- * best_model[q] = the winner (UINT32_MAX: no candidate, then every limb of its
+ * best_model[q] = the winner (MG_BV_NO_MODEL: no candidate, then every limb of its
  * values is all-ones), best_values[obj_off[q] + j] = its j-th objective,
  * cand_count[q] = the number of candidates.  Offsets start at 0 and do not
  * decrease, indices are below n_dags, a query lists at most MG_MIN_OBJ
@@ -656,17 +702,20 @@ int         mg_cc_open(mg_cc **out);
 void        mg_cc_close(mg_cc *cc);
 const char *mg_cc_error(mg_cc *cc);
 /* rows: n x {op, width, first_arg, n_args, imm}; op = a kernel-2 opcode
- * (bv_eval.cuh BV_*), or 0x1000 (variable: imm = its model-pool index) /
- * 0x1001 (constant: imm = its constant-pool index).  args[first_arg ..]: node
- * ids, or 0x80000000 | k for row k of this call.  ids[i] <- row i's id (an
- * equal existing node's id when there is one).  imm: the low bit of an
- * extract; table index | part << 20 | low bit << 21 of a table lookup.      */
+ * (MG_BV_*), or MG_CC_VAR (imm = its model-pool index) / MG_CC_CONST (imm =
+ * its constant-pool index).  args[first_arg ..]: node ids, or 0x80000000 | k
+ * for row k of this call.  ids[i] <- row i's id (an equal existing node's id
+ * when there is one).  imm: the low bit of an extract; a table lookup's
+ * MG_BV_TAB immediate.                                                      */
+#define MG_CC_VAR   0x1000u
+#define MG_CC_CONST 0x1001u
 int         mg_cc_add(mg_cc *cc, const uint32_t *rows, uint32_t n, const uint32_t *args, uint32_t n_args,
                       uint32_t *ids);
 /* The program of the conjunct rooted at node `root`: n_insns x 4 u32 into
  * insns (cap instructions); *max_slots is raised to the slots it uses.
- * MG_EUNSUPPORTED: more than 16 live values, more than 2048 instructions or
- * a value wider than 256 bits (the set stays with the SMT backend).        */
+ * MG_EUNSUPPORTED: more than MG_BV_MAX_SLOTS live values, more than
+ * MG_BV_TILE_INSNS instructions or a value wider than 256 bits (the set stays
+ * with the SMT backend).                                                    */
 int         mg_cc_compile(mg_cc *cc, uint32_t root, uint32_t *insns, uint32_t cap, uint32_t *n_insns,
                           uint32_t *max_slots);
 

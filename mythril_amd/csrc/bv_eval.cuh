@@ -28,35 +28,15 @@
 #include "u256.cuh"
 #include "../../include/mythgpu.h"
 
-enum BvOp : uint32_t {
-    BV_COPY = 0,       // acc = A
-    BV_ADD, BV_SUB, BV_MUL, BV_UDIV, BV_UREM, BV_SDIV, BV_SREM, BV_SMOD,
-    BV_AND, BV_OR, BV_XOR, BV_NOT, BV_NEG, BV_SHL, BV_LSHR, BV_ASHR,
-    BV_EQ, BV_ULT, BV_ULE, BV_UGT, BV_UGE, BV_SLT, BV_SLE, BV_SGT, BV_SGE,   // w3 = operand width
-    BV_BAND, BV_BOR, BV_BXOR, BV_BNOT, BV_BIMPLIES,
-    BV_ITE,            // A cond, B then, C else
-    BV_EXTRACT,        // A, w2 = lo
-    BV_CONCAT,         // A high, B low, w3 = width of B
-    BV_ZEXT,           // A (value already masked)
-    BV_SEXT,           // A, w2 = source width
-    BV_ADD_NOOVF_U,    // bvadd_noovfl unsigned; w3 = operand width
-    BV_MUL_NOOVF_U,    // bvumul_noovfl;        w3 = operand width
-    BV_SUB_NOUDF_U,    // BVSubNoUnderflow unsigned: b <= a
-    BV_NE,             // w3 = operand width
-    BV_TAB,            // A = key k0, B = key k1, w3 = table | part << 20 | lo << 21:
-                       // bits [256 part + lo, +width) of the model's array / function
-                       // interpretation at (k0, k1), else its default (lower.py)
-    BV_UMIN, BV_UMAX,  // ite(cmp(A, B), A, B) folded by the compiler (flatten._fold_select)
-    BV_SMIN, BV_SMAX,  // signed at `width`
-    BV_RSUB,           // B - A           (operand-swapped forms: the accumulator is only
-    BV_RCONCAT,        // A low, B high,   ever operand A; w3 = width of A)
-    BV_NUM_OPS,
+// The ABI's opcodes are the MG_BV_* of include/mythgpu.h (MG_BV_OP_LIST); these
+// are the library's own forms, numbered after them.
+enum BvFusedOp : uint32_t {
     // fused pairs, formed by bv_upload from adjacent instructions (never accepted
     // at the C-ABI): the first's result feeds only the second's accumulator, so one
     // dispatch does both and the 0/1 or 128-bit intermediate is never widened to
     // a 256-bit accumulator.  MG_BV_FUSE=0 uploads the programs unfused.
-    BV_CMP_BAND = BV_NUM_OPS,   // cmp(A, B) & C: w0 bits 22..27 = the comparison, width = its
-                                // operand width (w3 of the comparison); C = the and's B
+    BV_CMP_BAND = MG_BV_NUM_OPS,   // cmp(A, B) & C: w0 bits 22..27 = the comparison, width = its
+                                   // operand width (w3 of the comparison); C = the and's B
     BV_EXT_RCAT,                // rconcat(extract(A, lo, ew), B): w3 = shift | lo << 9 | ew << 17
     BV_BIN2,                    // op2(op1(A, B), C) for two 256-bit ops of bv_simple: w0 bits
                                 // 22..25 = op1, 26..29 = op2 (bv_simple indices); C = op2's B
@@ -65,13 +45,8 @@ enum BvOp : uint32_t {
     BV_NUM_INTERNAL
 };
 
-#define BV_REF_ACC 0u
-#define BV_REF_SLOT 1u
-#define BV_REF_VAR 2u
-#define BV_REF_CONST 3u
-#define BV_MAX_SLOTS 16u    // 4-bit slot field; 16 slots = 128 KiB of LDS per block
-#define BV_BLOCK 256u
-#define BV_TILE_INSNS 2048u   // longest program (LDS tile upper bound: 32 KiB)
+#define BV_BLOCK 256u          // 16 slots (MG_BV_MAX_SLOTS) = 128 KiB of LDS per block; the longest
+                               // program (MG_BV_TILE_INSNS) is a 32 KiB LDS tile
 #ifndef BV_TILE_MIN
 #define BV_TILE_MIN 256u      // smallest program tile (4 KiB in LDS)
 #endif
@@ -197,7 +172,8 @@ DEV bool bv_fits32(const U256 &a) {
 
 // model interpretation lookup (entries are unique keys: first match wins)
 DEV U256 bv_table(const BvCtx &c, const U256 &k0, const U256 &k1, uint32_t imm) {
-    const uint32_t t = imm & 0xfffffu, part = (imm >> 20) & 1u, lo = (imm >> 21) & 0xffu;
+    const uint32_t t = imm & MG_BV_TAB_INDEX_MASK, part = (imm >> MG_BV_TAB_PART_SHIFT) & 1u,
+                   lo = (imm >> MG_BV_TAB_LO_SHIFT) & 0xffu;
     const size_t tm = (size_t)t * c.n_models + c.model();
     const uint32_t s0 = c.tab.start[tm], cnt = c.tab.count[tm];
     U256 v = ld2(c.tab.dflt + tm * 4u + part * 2u);
@@ -223,7 +199,7 @@ DEV U256 bv_table(const BvCtx &c, const U256 &k0, const U256 &k1, uint32_t imm) 
 DEV U256 bv_fetch(const BvCtx &c, uint32_t ref) {
     const uint32_t kind = ref >> 30, idx = ref & 0x3fffffffu;
     U256 r;
-    if (kind == BV_REF_VAR) {            // the commonest B operand (C4: 46 %) first
+    if (kind == MG_BV_REF_VAR) {            // the commonest B operand (C4: 46 %) first
         // a 32-bit byte offset from the table's base (bv_upload keeps the table
         // under 4 GiB): the uniform part is one scalar multiply, the load takes the
         // base as its SGPR address
@@ -235,7 +211,7 @@ DEV U256 bv_fetch(const BvCtx &c, uint32_t ref) {
         BV_PIN("; variable operand", r);
         return r;
     }
-    if (kind <= BV_REF_SLOT) {
+    if (kind <= MG_BV_REF_SLOT) {
         const uint4 x = c.lane_slots[(idx * 2u) * BV_BLOCK];
         const uint4 y = c.lane_slots[(idx * 2u + 1u) * BV_BLOCK];
         r.w[0] = x.x; r.w[1] = x.y; r.w[2] = x.z; r.w[3] = x.w;
@@ -268,9 +244,9 @@ DEV U256 bv_udivrem(bool quotient, const U256 &A, const U256 &B) {
     if (!bv_iszero(B)) u_divmod_nz_t<true>(A, B, q, r);
     return quotient ? q : r;
 }
-#define BV_DIV_OPS ((1ull << BV_SDIV) | (1ull << BV_SREM) | (1ull << BV_SMOD) | (1ull << BV_MUL_NOOVF_U))
+#define BV_DIV_OPS ((1ull << MG_BV_SDIV) | (1ull << MG_BV_SREM) | (1ull << MG_BV_SMOD) | (1ull << MG_BV_MUL_NOOVF_U))
 DEV U256 bv_divop(uint32_t op, uint32_t width, uint32_t rc, const U256 &A, const U256 &B) {
-    const bool sgn = op == BV_SDIV || op == BV_SREM || op == BV_SMOD;   // wave-uniform
+    const bool sgn = op == MG_BV_SDIV || op == MG_BV_SREM || op == MG_BV_SMOD;   // wave-uniform
     U256 a = A, b = B;
     bool na = false, nb = false;
     if (sgn) {                                  // magnitudes of the width-bit signed operands
@@ -282,16 +258,16 @@ DEV U256 bv_divop(uint32_t op, uint32_t width, uint32_t rc, const U256 &A, const
         if (nb) b = u_neg(b);
     }
     U256 keep = b;                              // divisor magnitude (SMOD) / B (MUL_NOOVF_U)
-    if (op == BV_MUL_NOOVF_U) { keep = B; b = A; a = bv_mask(u_ones(), rc); }
+    if (op == MG_BV_MUL_NOOVF_U) { keep = B; b = A; a = bv_mask(u_ones(), rc); }
     const bool bz = bv_iszero(b);
     U256 q = u_ones(), r = a;                   // b == 0: q = ones, r = a
     if (!bz) u_divmod_nz_t<true>(a, b, q, r);
     switch (op) {
-    case BV_UDIV: return q;
-    case BV_UREM: return r;
-    case BV_SDIV: return bz ? (na ? u_small(1) : u_ones()) : ((na != nb) ? u_neg(q) : q);
-    case BV_SREM: return na ? u_neg(r) : r;     // b == 0: the signed dividend
-    case BV_SMOD: {
+    case MG_BV_UDIV: return q;
+    case MG_BV_UREM: return r;
+    case MG_BV_SDIV: return bz ? (na ? u_small(1) : u_ones()) : ((na != nb) ? u_neg(q) : q);
+    case MG_BV_SREM: return na ? u_neg(r) : r;     // b == 0: the signed dividend
+    case MG_BV_SMOD: {
         const U256 s = na ? u_neg(r) : r;       // srem: sign of the dividend
         if (bz || bv_iszero(s) || u_isneg(s) == nb) return s;
         return u_add(s, nb ? u_neg(keep) : keep);   // smod: sign of the divisor
@@ -303,27 +279,27 @@ DEV U256 bv_divop(uint32_t op, uint32_t width, uint32_t rc, const U256 &A, const
 
 // ops whose 256-bit result may have bits at or above `width`: only these are
 // masked (the comparisons, Boolean connectives and overflow tests produce 0/1)
-#define BV_MASK_OPS ((1ull << BV_COPY) | (1ull << BV_ADD) | (1ull << BV_SUB) | (1ull << BV_MUL) | \
-                     (1ull << BV_UDIV) | (1ull << BV_SDIV) | (1ull << BV_SREM) | (1ull << BV_SMOD) | \
-                     (1ull << BV_NOT) | (1ull << BV_NEG) | (1ull << BV_SHL) | (1ull << BV_ASHR) | \
-                     (1ull << BV_EXTRACT) | (1ull << BV_CONCAT) | (1ull << BV_SEXT) | (1ull << BV_ITE) | \
-                     (1ull << BV_TAB) | (1ull << BV_SMIN) | (1ull << BV_SMAX) | (1ull << BV_ZEXT) | \
-                     (1ull << BV_AND) | (1ull << BV_OR) | (1ull << BV_XOR) | (1ull << BV_LSHR) | \
-                     (1ull << BV_UREM) | (1ull << BV_UMIN) | (1ull << BV_UMAX) | (1ull << BV_RSUB) | \
-                     (1ull << BV_RCONCAT) | (1ull << BV_EXT_RCAT))
+#define BV_MASK_OPS ((1ull << MG_BV_COPY) | (1ull << MG_BV_ADD) | (1ull << MG_BV_SUB) | (1ull << MG_BV_MUL) | \
+                     (1ull << MG_BV_UDIV) | (1ull << MG_BV_SDIV) | (1ull << MG_BV_SREM) | (1ull << MG_BV_SMOD) | \
+                     (1ull << MG_BV_NOT) | (1ull << MG_BV_NEG) | (1ull << MG_BV_SHL) | (1ull << MG_BV_ASHR) | \
+                     (1ull << MG_BV_EXTRACT) | (1ull << MG_BV_CONCAT) | (1ull << MG_BV_SEXT) | (1ull << MG_BV_ITE) | \
+                     (1ull << MG_BV_TAB) | (1ull << MG_BV_SMIN) | (1ull << MG_BV_SMAX) | (1ull << MG_BV_ZEXT) | \
+                     (1ull << MG_BV_AND) | (1ull << MG_BV_OR) | (1ull << MG_BV_XOR) | (1ull << MG_BV_LSHR) | \
+                     (1ull << MG_BV_UREM) | (1ull << MG_BV_UMIN) | (1ull << MG_BV_UMAX) | (1ull << MG_BV_RSUB) | \
+                     (1ull << MG_BV_RCONCAT) | (1ull << BV_EXT_RCAT))
 
 // Predecode (bv_predecode, at upload, after bv_fuse): flags the kernel tests
 // with one scalar bit test instead of deriving them from op and width per
 // instruction -- op byte bit 7: the op has one operand (no B fetch, the small
 // switch); w0 bit 30: the result is masked to `width` (width < 256 and the op
 // in BV_MASK_OPS).  Internal to the library: the C-ABI's programs never carry
-// them (bv_upload rejects bits 22..31, and op < BV_NUM_OPS < 128).
+// them (bv_upload rejects bits 22..31, and op < MG_BV_NUM_OPS < 128).
 #define BV_W0_UNARY 0x80u
 #define BV_W0_HOT 0x40u
 #define BV_W0_MASK (1u << 30)
 static bool bv_is_unary(uint32_t op) {
-    return op == BV_COPY || op == BV_NOT || op == BV_NEG || op == BV_BNOT || op == BV_EXTRACT || op == BV_ZEXT ||
-           op == BV_SEXT;
+    return op == MG_BV_COPY || op == MG_BV_NOT || op == MG_BV_NEG || op == MG_BV_BNOT || op == MG_BV_EXTRACT || op == MG_BV_ZEXT ||
+           op == MG_BV_SEXT;
 }
 static void bv_predecode(std::vector<uint32_t> &v, const std::vector<uint32_t> &off, uint32_t n) {
     for (uint32_t d = 0; d < n; ++d) {
@@ -333,7 +309,7 @@ static void bv_predecode(std::vector<uint32_t> &v, const std::vector<uint32_t> &
             if (bv_is_unary(op)) w0 |= BV_W0_UNARY;
             // each group's commonest op (C4: extract 13 % of the fused instructions,
             // cmp-and 19 %) is tested by this bit before the group's switch
-            if (op == BV_EXTRACT || op == BV_CMP_BAND) w0 |= BV_W0_HOT;
+            if (op == MG_BV_EXTRACT || op == BV_CMP_BAND) w0 |= BV_W0_HOT;
             if (width < 256u && op < 64u && ((BV_MASK_OPS >> op) & 1ull)) w0 |= BV_W0_MASK;
             if (op == BV_BINX || (w0 >> 31)) ++i;      // skip the extension slot
         }
@@ -363,12 +339,13 @@ __device__ __forceinline__ U256 bv_simple(uint32_t k, const U256 &a, const U256 
     case 3: return u_and(a, b);
     case 4: return u_or(a, b);
     case 5: return u_xor(a, b);
-    case 6: return u_select(u_lt(a, b), b, a);     // BV_UMAX
-    case 7: return u_select(u_lt(b, a), b, a);     // BV_UMIN
-    default: return u_sub(b, a);                   // BV_RSUB
+    case 6: return u_select(u_lt(a, b), b, a);     // MG_BV_UMAX
+    case 7: return u_select(u_lt(b, a), b, a);     // MG_BV_UMIN
+    default: return u_sub(b, a);                   // MG_BV_RSUB
     }
 }
-static const uint32_t kBvSimple[9] = {BV_ADD, BV_SUB, BV_MUL, BV_AND, BV_OR, BV_XOR, BV_UMAX, BV_UMIN, BV_RSUB};
+static const uint32_t kBvSimple[9] = {MG_BV_ADD, MG_BV_SUB, MG_BV_MUL, MG_BV_AND, MG_BV_OR,
+                                      MG_BV_XOR, MG_BV_UMAX, MG_BV_UMIN, MG_BV_RSUB};
 
 __global__ BV_BOUNDS void k_bv_eval(const uint4 *__restrict__ insns,
                                                       const uint32_t *__restrict__ prog_off,
@@ -417,7 +394,6 @@ __global__ BV_BOUNDS void k_bv_terms(const uint4 *__restrict__ insns,
 // (k <= 8 objectives would be 64 VGPRs per tuple; these launches are small and
 // latency-bound) -- over its strided models first, then across the wave's 64
 // lanes by shuffles of the index, then across the block's waves through LDS.
-#define BV_NO_MODEL 0xffffffffu
 struct BvMinQuery {
     const uint4 *__restrict__ values;        // [n_dags][n_models][2]
     const uint32_t *__restrict__ obj;        // the query's objective DAGs
@@ -425,9 +401,9 @@ struct BvMinQuery {
     DEV const uint4 *row(uint32_t dag, uint32_t m) const {
         return reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(values) + (dag * n_models + m) * 32u);
     }
-    // is model a's (tuple, index) smaller than b's?  BV_NO_MODEL is larger than any model
+    // is model a's (tuple, index) smaller than b's?  MG_BV_NO_MODEL is larger than any model
     DEV bool less(uint32_t a, uint32_t b) const {
-        if (a == BV_NO_MODEL || b == BV_NO_MODEL) return a != BV_NO_MODEL;
+        if (a == MG_BV_NO_MODEL || b == MG_BV_NO_MODEL) return a != MG_BV_NO_MODEL;
         if (a == b) return false;
         for (uint32_t j = 0; j < n_obj; ++j) {
             const uint32_t dag = obj[j];
@@ -450,7 +426,7 @@ __global__ __launch_bounds__(BV_BLOCK) void k_bv_lexmin(const uint4 *__restrict_
     const uint32_t q = blockIdx.x, tid = threadIdx.x;
     const uint32_t c0 = cons_off[q], c1 = cons_off[q + 1], o0 = obj_off[q], o1 = obj_off[q + 1];
     const BvMinQuery Q{values, obj_dag + o0, o1 - o0, n_models};
-    uint32_t best = BV_NO_MODEL, cnt = 0u;
+    uint32_t best = MG_BV_NO_MODEL, cnt = 0u;
     for (uint32_t m = tid; m < n_models; m += BV_BLOCK) {      // ascending: a tie keeps the earlier model
         uint32_t ok = 1u;
         for (uint32_t k = c0; k < c1; ++k) ok &= Q.row(cons_dag[k], m)->x;
@@ -474,7 +450,7 @@ __global__ __launch_bounds__(BV_BLOCK) void k_bv_lexmin(const uint4 *__restrict_
     if (tid == 0u) { best_model[q] = best; cand_count[q] = cnt; }
     if (tid < Q.n_obj * 8u) {                                   // <= MG_MIN_OBJ * 8 = 64 limbs
         const uint32_t j = tid >> 3, l = tid & 7u;
-        best_values[(o0 + j) * 8u + l] = best == BV_NO_MODEL ? 0xffffffffu :
+        best_values[(o0 + j) * 8u + l] = best == MG_BV_NO_MODEL ? 0xffffffffu :
             reinterpret_cast<const uint32_t *>(Q.row(Q.obj[j], best))[l];
     }
 }
@@ -530,9 +506,9 @@ static void bv_fuse(const mg_dag_batch *dags, std::vector<uint32_t> &out, std::v
                 const uint32_t *q = p + 4;
                 const uint32_t op2 = q[0] & 0xffu, w2 = (q[0] >> 8) & 0x1ffu;
                 const uint32_t keep2 = q[0] & (0x1fu << 17);          // the second's store bit + slot
-                const bool acc2 = (q[1] >> 30) == BV_REF_ACC;
-                const bool cmp = (op >= BV_EQ && op <= BV_SGE) || op == BV_NE;
-                if (acc2 && cmp && op2 == BV_BAND && p[3] >= 1u && p[3] <= 256u) {
+                const bool acc2 = (q[1] >> 30) == MG_BV_REF_ACC;
+                const bool cmp = (op >= MG_BV_EQ && op <= MG_BV_SGE) || op == MG_BV_NE;
+                if (acc2 && cmp && op2 == MG_BV_BAND && p[3] >= 1u && p[3] <= 256u) {
                     const uint32_t w = (p[3] & 0x1ffu);
                     const uint32_t f[4] = {BV_CMP_BAND | (w << 8) | keep2 | (op << 22), p[1], p[2], q[2]};
                     out.insert(out.end(), f, f + 4);
@@ -548,7 +524,7 @@ static void bv_fuse(const mg_dag_batch *dags, std::vector<uint32_t> &out, std::v
                     while (binx && L < 4 && i + L < b && ((dags->insns[4 * (size_t)(i + L - 1)] >> 17) & 1u) == 0u) {
                         const uint32_t *x = dags->insns + 4 * (size_t)(i + L);
                         const int sx = bv_simple_index(x[0] & 0xffu);
-                        if (sx < 0 || ((x[0] >> 8) & 0x1ffu) != 256u || (x[1] >> 30) != BV_REF_ACC) break;
+                        if (sx < 0 || ((x[0] >> 8) & 0x1ffu) != 256u || (x[1] >> 30) != MG_BV_REF_ACC) break;
                         kinds |= (uint32_t)sx << (4 * L);
                         ++L;
                     }
@@ -567,7 +543,7 @@ static void bv_fuse(const mg_dag_batch *dags, std::vector<uint32_t> &out, std::v
                     ++i;
                     continue;
                 }
-                if (acc2 && tail && (s1 < 0 || w1 != 256u) && (w1 == 256u || narrow_tail) && op < BV_NUM_OPS &&
+                if (acc2 && tail && (s1 < 0 || w1 != 256u) && (w1 == 256u || narrow_tail) && op < MG_BV_NUM_OPS &&
                     s2 >= 0 && w2 == 256u) {
                     // any other op whose result feeds 1-3 256-bit bv_simple ops: the
                     // op keeps its own encoding, w0 bit 31 marks an extension slot
@@ -575,7 +551,7 @@ static void bv_fuse(const mg_dag_batch *dags, std::vector<uint32_t> &out, std::v
                     while (L < 3 && i + L + 1 < b && ((dags->insns[4 * (size_t)(i + L)] >> 17) & 1u) == 0u) {
                         const uint32_t *x = dags->insns + 4 * (size_t)(i + L + 1);
                         const int sx = bv_simple_index(x[0] & 0xffu);
-                        if (sx < 0 || ((x[0] >> 8) & 0x1ffu) != 256u || (x[1] >> 30) != BV_REF_ACC) break;
+                        if (sx < 0 || ((x[0] >> 8) & 0x1ffu) != 256u || (x[1] >> 30) != MG_BV_REF_ACC) break;
                         kinds |= (uint32_t)sx << (4 * L);
                         ++L;
                     }
@@ -587,7 +563,7 @@ static void bv_fuse(const mg_dag_batch *dags, std::vector<uint32_t> &out, std::v
                     i += L;
                     continue;
                 }
-                if (acc2 && op == BV_EXTRACT && op2 == BV_RCONCAT && q[3] < 512u) {
+                if (acc2 && op == MG_BV_EXTRACT && op2 == MG_BV_RCONCAT && q[3] < 512u) {
                     const uint32_t ew = (p[0] >> 8) & 0x1ffu;
                     const uint32_t f[4] = {BV_EXT_RCAT | (w2 << 8) | keep2, p[1], q[2],
                                            q[3] | ((p[2] & 0xffu) << 9) | (ew << 17)};
@@ -605,7 +581,7 @@ static void bv_fuse(const mg_dag_batch *dags, std::vector<uint32_t> &out, std::v
 static int bv_upload(BvState &s, const mg_dag_batch *dags, const mg_model_batch *models, hipStream_t st,
                      std::string &msg) {
     if (dags->n_dags == 0 || !dags->prog_off || !dags->insns) { msg = "empty DAG batch"; return MG_EINVAL; }
-    if (dags->n_slots > BV_MAX_SLOTS) { msg = "too many slots"; return MG_EINVAL; }
+    if (dags->n_slots > MG_BV_MAX_SLOTS) { msg = "too many slots"; return MG_EINVAL; }
     if ((uint64_t)dags->n_consts * 32u >= (1ull << 32)) { msg = "constant table over 4 GiB"; return MG_EINVAL; }
     if (models->n_models == 0 || (models->n_vars && !models->values)) { msg = "empty model batch"; return MG_EINVAL; }
     if ((uint64_t)models->n_vars * models->n_models * 32u >= (1ull << 32)) {
@@ -617,33 +593,36 @@ static int bv_upload(BvState &s, const mg_dag_batch *dags, const mg_model_batch 
     // validate programs on the host: refs in range, program fits a tile
     for (uint32_t d = 0; d < n; ++d) {
         const uint32_t a = dags->prog_off[d], b = dags->prog_off[d + 1];
-        if (b < a || b - a > BV_TILE_INSNS || b > total) { msg = "bad program offsets / program too long"; return MG_EINVAL; }
+        if (b < a || b - a > MG_BV_TILE_INSNS || b > total) {
+            msg = "bad program offsets / program too long";
+            return MG_EINVAL;
+        }
     }
     for (uint32_t i = 0; i < total; ++i) {
         const uint32_t *w = dags->insns + 4 * (size_t)i;
         const uint32_t op = w[0] & 0xffu, width = (w[0] >> 8) & 0x1ffu;
-        if (op >= BV_NUM_OPS || width == 0 || width > 256 || (w[0] >> 22) != 0u) {
+        if (op >= MG_BV_NUM_OPS || width == 0 || width > 256 || (w[0] >> 22) != 0u) {
             msg = "bad instruction " + std::to_string(i);   // bits 22..31 are the fused forms'
             return MG_EINVAL;
         }
         if (((w[0] >> 17) & 1u) && ((w[0] >> 18) & 0xfu) >= dags->n_slots) { msg = "slot out of range"; return MG_EINVAL; }
-        if (op == BV_TAB) {
-            const uint32_t imm = w[3], t = imm & 0xfffffu, lo = (imm >> 21) & 0xffu;
+        if (op == MG_BV_TAB) {
+            const uint32_t imm = w[3], t = imm & MG_BV_TAB_INDEX_MASK, lo = (imm >> MG_BV_TAB_LO_SHIFT) & 0xffu;
             if (t >= models->n_tables || (imm >> 29) != 0u || lo + width > 256u) {
                 msg = "bad table reference at instruction " + std::to_string(i);
                 return MG_EINVAL;
             }
         }
-        const int nref = (op == BV_ITE) ? 3 : (op == BV_COPY || op == BV_NOT || op == BV_NEG || op == BV_BNOT ||
-                                               op == BV_EXTRACT || op == BV_ZEXT || op == BV_SEXT) ? 1 : 2;
+        const int nref = (op == MG_BV_ITE) ? 3 : (op == MG_BV_COPY || op == MG_BV_NOT || op == MG_BV_NEG || op == MG_BV_BNOT ||
+                                               op == MG_BV_EXTRACT || op == MG_BV_ZEXT || op == MG_BV_SEXT) ? 1 : 2;
         for (int k = 0; k < nref; ++k) {
             const uint32_t ref = w[1 + k], kind = ref >> 30, idx = ref & 0x3fffffffu;
-            if (k > 0 && kind == BV_REF_ACC) {
+            if (k > 0 && kind == MG_BV_REF_ACC) {
                 msg = "accumulator operand past position A at instruction " + std::to_string(i);
                 return MG_EINVAL;
             }
-            if ((kind == BV_REF_SLOT && idx >= dags->n_slots) || (kind == BV_REF_VAR && idx >= models->n_vars) ||
-                (kind == BV_REF_CONST && idx >= dags->n_consts)) {
+            if ((kind == MG_BV_REF_SLOT && idx >= dags->n_slots) || (kind == MG_BV_REF_VAR && idx >= models->n_vars) ||
+                (kind == MG_BV_REF_CONST && idx >= dags->n_consts)) {
                 msg = "operand out of range at instruction " + std::to_string(i);
                 return MG_EINVAL;
             }
@@ -665,7 +644,7 @@ static int bv_upload(BvState &s, const mg_dag_batch *dags, const mg_model_batch 
     insns = s.h_insns.data();
     prog_off = s.h_off.data();
     total_up = s.h_off[n];
-    // tiles: consecutive DAGs whose programs fit BV_TILE_INSNS together
+    // tiles: consecutive DAGs whose programs fit MG_BV_TILE_INSNS together
     // LDS tile capacity: the longest program rounded up, at least BV_TILE_MIN, so
     // short-program batches keep a small LDS footprint (higher occupancy)
     uint32_t longest = 0;
@@ -783,7 +762,7 @@ static int bv_run(BvState &s, uint32_t dag_first, uint32_t dag_count, hipStream_
     static bool lds_attr = false;      // programs with more than 4 slots need > 64 KiB of LDS
     if (!lds_attr) {
         (void)hipFuncSetAttribute((const void *)k_bv_eval, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)(BV_MAX_SLOTS * 2 * BV_BLOCK * sizeof(uint4)));
+                                  (int)(MG_BV_MAX_SLOTS * 2 * BV_BLOCK * sizeof(uint4)));
         lds_attr = true;
     }
     hipLaunchKernelGGL(k_bv_eval, dim3((unsigned)grid), dim3(BV_BLOCK), lds, st,
@@ -829,7 +808,7 @@ static int bv_terms(BvState &s, hipStream_t st, std::string &msg) {
     static bool lds_attr = false;      // programs with more than 4 slots need > 64 KiB of LDS
     if (!lds_attr) {
         (void)hipFuncSetAttribute((const void *)k_bv_terms, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)(BV_MAX_SLOTS * 2 * BV_BLOCK * sizeof(uint4)));
+                                  (int)(MG_BV_MAX_SLOTS * 2 * BV_BLOCK * sizeof(uint4)));
         lds_attr = true;
     }
     hipLaunchKernelGGL(k_bv_terms, dim3((unsigned)g.grid), dim3(BV_BLOCK), g.lds, st,

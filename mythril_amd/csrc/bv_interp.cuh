@@ -63,19 +63,19 @@
             }
             // op byte bit 7 = one operand (bv_predecode); w0 bit 30 = mask to width
             const uint32_t op = w0 & 0x3fu, width = (w0 >> 8) & 0x1ffu;
-            if ((ra >> 30) != BV_REF_ACC) acc = bv_fetch(c, ra);    // A in the accumulator's registers
+            if ((ra >> 30) != MG_BV_REF_ACC) acc = bv_fetch(c, ra);    // A in the accumulator's registers
             const U256 A = acc;
             U256 r;
             if (w0 & BV_W0_UNARY) {
                 if (w0 & BV_W0_HOT) {
-                    r = u_shr_u(A, rb & 0xffu, 0u);                              // BV_EXTRACT
+                    r = u_shr_u(A, rb & 0xffu, 0u);                              // MG_BV_EXTRACT
                 } else {
                 switch (op) {
-                case BV_NOT: r = u_not(A); break;
-                case BV_NEG: r = u_neg(A); break;
-                case BV_BNOT: r = u_small((A.w[0] & 1u) ^ 1u); break;
-                case BV_SEXT: r = bv_sext(A, rb); break;
-                default: r = A; break;                                          // BV_COPY, BV_ZEXT
+                case MG_BV_NOT: r = u_not(A); break;
+                case MG_BV_NEG: r = u_neg(A); break;
+                case MG_BV_BNOT: r = u_small((A.w[0] & 1u) ^ 1u); break;
+                case MG_BV_SEXT: r = bv_sext(A, rb); break;
+                default: r = A; break;                                          // MG_BV_COPY, MG_BV_ZEXT
                 }
                 }
             } else {
@@ -84,36 +84,36 @@
                     const uint32_t sub = (w0 >> 22) & 0x3fu;
                     bool t;
                     switch (sub) {
-                    case BV_EQ: t = bv_eq(A, B); break;
-                    case BV_NE: t = !bv_eq(A, B); break;
-                    case BV_ULT: t = u_lt(A, B); break;
-                    case BV_ULE: t = !u_lt(B, A); break;
-                    case BV_UGT: t = u_lt(B, A); break;
-                    case BV_UGE: t = !u_lt(A, B); break;
-                    case BV_SLT: t = u_slt(bv_sext(A, width), bv_sext(B, width)); break;
-                    case BV_SLE: t = !u_slt(bv_sext(B, width), bv_sext(A, width)); break;
-                    case BV_SGT: t = u_slt(bv_sext(B, width), bv_sext(A, width)); break;
-                    default: t = !u_slt(bv_sext(A, width), bv_sext(B, width)); break;   // BV_SGE
+                    case MG_BV_EQ: t = bv_eq(A, B); break;
+                    case MG_BV_NE: t = !bv_eq(A, B); break;
+                    case MG_BV_ULT: t = u_lt(A, B); break;
+                    case MG_BV_ULE: t = !u_lt(B, A); break;
+                    case MG_BV_UGT: t = u_lt(B, A); break;
+                    case MG_BV_UGE: t = !u_lt(A, B); break;
+                    case MG_BV_SLT: t = u_slt(bv_sext(A, width), bv_sext(B, width)); break;
+                    case MG_BV_SLE: t = !u_slt(bv_sext(B, width), bv_sext(A, width)); break;
+                    case MG_BV_SGT: t = u_slt(bv_sext(B, width), bv_sext(A, width)); break;
+                    default: t = !u_slt(bv_sext(A, width), bv_sext(B, width)); break;   // MG_BV_SGE
                     }
                     const U256 C = bv_fetch(c, rc);
                     r = u_small((t ? 1u : 0u) & C.w[0]);
-                } else if (op == BV_UDIV || op == BV_UREM) {        // the unsigned division site
-                    r = bv_udivrem(op == BV_UDIV, A, B);
+                } else if (op == MG_BV_UDIV || op == MG_BV_UREM) {        // the unsigned division site
+                    r = bv_udivrem(op == MG_BV_UDIV, A, B);
                 } else if ((BV_DIV_OPS >> op) & 1ull) {      // the signed / overflow site
                     r = bv_divop(op, width, rc, A, B);
                 } else {
                 switch (op) {
-                case BV_ADD: r = u_add(A, B); break;
-                case BV_SUB: r = u_sub(A, B); break;
-                case BV_MUL: r = u_mul(A, B); break;
-                case BV_AND: r = u_and(A, B); break;
-                case BV_OR: r = u_or(A, B); break;
-                case BV_XOR: r = u_xor(A, B); break;
-                case BV_SHL: case BV_LSHR: case BV_ASHR: {
+                case MG_BV_ADD: r = u_add(A, B); break;
+                case MG_BV_SUB: r = u_sub(A, B); break;
+                case MG_BV_MUL: r = u_mul(A, B); break;
+                case MG_BV_AND: r = u_and(A, B); break;
+                case MG_BV_OR: r = u_or(A, B); break;
+                case MG_BV_XOR: r = u_xor(A, B); break;
+                case MG_BV_SHL: case MG_BV_LSHR: case MG_BV_ASHR: {
                     // a constant shift amount is wave-uniform: scalar-branch shifts
-                    const bool ub = (rb >> 30) == BV_REF_CONST;
+                    const bool ub = (rb >> 30) == MG_BV_REF_CONST;
                     const bool in = bv_fits32(B) && B.w[0] < width;
-                    if (op == BV_ASHR) {
+                    if (op == MG_BV_ASHR) {
                         const U256 sa = bv_sext(A, width);
                         const uint32_t fill = u_isneg(sa) ? 0xffffffffu : 0u;
                         if (ub) {
@@ -124,47 +124,47 @@
                         }
                     } else if (ub) {
                         if (!uni(in ? 1u : 0u)) r = u_zero();
-                        else if (op == BV_SHL) r = u_shl_u(A, uni(B.w[0]));
+                        else if (op == MG_BV_SHL) r = u_shl_u(A, uni(B.w[0]));
                         else r = u_shr_u(A, uni(B.w[0]), 0u);
                     } else {
-                        r = !in ? u_zero() : op == BV_SHL ? u_shl_n(A, B.w[0]) : u_shr_n(A, B.w[0], 0u);
+                        r = !in ? u_zero() : op == MG_BV_SHL ? u_shl_n(A, B.w[0]) : u_shr_n(A, B.w[0], 0u);
                     }
                     break;
                 }
-                case BV_EQ: r = u_small(bv_eq(A, B)); break;
-                case BV_NE: r = u_small(!bv_eq(A, B)); break;
-                case BV_ULT: r = u_small(u_lt(A, B)); break;
-                case BV_ULE: r = u_small(!u_lt(B, A)); break;
-                case BV_UGT: r = u_small(u_lt(B, A)); break;
-                case BV_UGE: r = u_small(!u_lt(A, B)); break;
-                case BV_SLT: r = u_small(u_slt(bv_sext(A, rc), bv_sext(B, rc))); break;
-                case BV_SLE: r = u_small(!u_slt(bv_sext(B, rc), bv_sext(A, rc))); break;
-                case BV_SGT: r = u_small(u_slt(bv_sext(B, rc), bv_sext(A, rc))); break;
-                case BV_SGE: r = u_small(!u_slt(bv_sext(A, rc), bv_sext(B, rc))); break;
-                case BV_BAND: r = u_small(A.w[0] & B.w[0] & 1u); break;
-                case BV_BOR: r = u_small((A.w[0] | B.w[0]) & 1u); break;
-                case BV_BXOR: r = u_small((A.w[0] ^ B.w[0]) & 1u); break;
-                case BV_BIMPLIES: r = u_small(((A.w[0] & 1u) ^ 1u) | (B.w[0] & 1u)); break;
-                case BV_ITE: {
+                case MG_BV_EQ: r = u_small(bv_eq(A, B)); break;
+                case MG_BV_NE: r = u_small(!bv_eq(A, B)); break;
+                case MG_BV_ULT: r = u_small(u_lt(A, B)); break;
+                case MG_BV_ULE: r = u_small(!u_lt(B, A)); break;
+                case MG_BV_UGT: r = u_small(u_lt(B, A)); break;
+                case MG_BV_UGE: r = u_small(!u_lt(A, B)); break;
+                case MG_BV_SLT: r = u_small(u_slt(bv_sext(A, rc), bv_sext(B, rc))); break;
+                case MG_BV_SLE: r = u_small(!u_slt(bv_sext(B, rc), bv_sext(A, rc))); break;
+                case MG_BV_SGT: r = u_small(u_slt(bv_sext(B, rc), bv_sext(A, rc))); break;
+                case MG_BV_SGE: r = u_small(!u_slt(bv_sext(A, rc), bv_sext(B, rc))); break;
+                case MG_BV_BAND: r = u_small(A.w[0] & B.w[0] & 1u); break;
+                case MG_BV_BOR: r = u_small((A.w[0] | B.w[0]) & 1u); break;
+                case MG_BV_BXOR: r = u_small((A.w[0] ^ B.w[0]) & 1u); break;
+                case MG_BV_BIMPLIES: r = u_small(((A.w[0] & 1u) ^ 1u) | (B.w[0] & 1u)); break;
+                case MG_BV_ITE: {
                     const U256 C = bv_fetch(c, rc);
                     r = u_select((A.w[0] & 1u) != 0u, B, C);
                     break;
                 }
-                case BV_CONCAT: r = u_or(u_shl_u(A, rc), B); break;                 // rc: uniform
-                case BV_ADD_NOOVF_U: {  // top bit of the (w+1)-bit sum is 0
+                case MG_BV_CONCAT: r = u_or(u_shl_u(A, rc), B); break;                 // rc: uniform
+                case MG_BV_ADD_NOOVF_U: {  // top bit of the (w+1)-bit sum is 0
                     const U256 s = u_add(A, B);
                     const bool ovf = rc >= 256u ? u_lt(s, A) : !bv_iszero(u_shr_u(s, rc, 0u));
                     r = u_small(!ovf);
                     break;
                 }
-                case BV_SUB_NOUDF_U: r = u_small(!u_lt(A, B)); break;
-                case BV_TAB: r = bv_table(c, A, B, rc); break;
-                case BV_UMIN: r = u_select(u_lt(B, A), B, A); break;
-                case BV_UMAX: r = u_select(u_lt(A, B), B, A); break;
-                case BV_SMIN: r = u_select(u_slt(bv_sext(B, width), bv_sext(A, width)), B, A); break;
-                case BV_SMAX: r = u_select(u_slt(bv_sext(A, width), bv_sext(B, width)), B, A); break;
-                case BV_RSUB: r = u_sub(B, A); break;
-                case BV_RCONCAT: r = u_or(u_shl_u(B, rc), A); break;
+                case MG_BV_SUB_NOUDF_U: r = u_small(!u_lt(A, B)); break;
+                case MG_BV_TAB: r = bv_table(c, A, B, rc); break;
+                case MG_BV_UMIN: r = u_select(u_lt(B, A), B, A); break;
+                case MG_BV_UMAX: r = u_select(u_lt(A, B), B, A); break;
+                case MG_BV_SMIN: r = u_select(u_slt(bv_sext(B, width), bv_sext(A, width)), B, A); break;
+                case MG_BV_SMAX: r = u_select(u_slt(bv_sext(A, width), bv_sext(B, width)), B, A); break;
+                case MG_BV_RSUB: r = u_sub(B, A); break;
+                case MG_BV_RCONCAT: r = u_or(u_shl_u(B, rc), A); break;
                 case BV_BIN2: {
                     const U256 t = bv_simple((w0 >> 22) & 0xfu, A, B);
                     const U256 C = bv_fetch(c, rc);

@@ -23,31 +23,22 @@
 #include <unordered_map>
 #include <vector>
 
+#include "../../include/mythgpu.h"   // MG_BV_* opcodes, operand kinds and limits; MG_CC_*
+
 namespace mgcc {
 
-// device opcodes (mythril_amd/smt/program.py OPS) the passes name
-enum : uint32_t {
-    O_COPY = 0, O_ADD = 1, O_SUB = 2, O_MUL = 3, O_AND_BV = 9, O_OR_BV = 10, O_XOR_BV = 11,
-    O_EQ = 17, O_ULT = 18, O_ULE = 19, O_UGT = 20, O_UGE = 21, O_SLT = 22, O_SLE = 23, O_SGT = 24, O_SGE = 25,
-    O_AND = 26, O_OR = 27, O_XOR = 28, O_NOT = 29, O_IMPLIES = 30, O_ITE = 31, O_EXTRACT = 32, O_CONCAT = 33,
-    O_ZEXT = 34, O_SEXT = 35, O_ADD_NOOVFL = 36, O_MUL_NOOVFL = 37, O_SUB_NOUDFL = 38, O_DISTINCT = 39,
-    O_TAB = 40, O_UMIN = 41, O_UMAX = 42, O_SMIN = 43, O_SMAX = 44, O_RSUB = 45, O_RCONCAT = 46,
-    N_DEVICE_OPS = 47,
-    O_VAR = 0x1000, O_CONST = 0x1001,
-};
-constexpr uint32_t MAX_SLOTS = 16, TILE_INSNS = 2048, WMAX = 256;
-constexpr uint32_t REF_ACC = 0, REF_SLOT = 1, REF_VAR = 2, REF_CONST = 3;
+constexpr uint32_t WMAX = 256;
 constexpr uint32_t NONE = 0xffffffffu;
 
 inline bool is_cmp(uint32_t op) {
-    return op == O_EQ || op == O_DISTINCT || (op >= O_ULT && op <= O_SGE) || op == O_ADD_NOOVFL ||
-           op == O_MUL_NOOVFL || op == O_SUB_NOUDFL;
+    return op == MG_BV_EQ || op == MG_BV_NE || (op >= MG_BV_ULT && op <= MG_BV_SGE) || op == MG_BV_ADD_NOOVF_U ||
+           op == MG_BV_MUL_NOOVF_U || op == MG_BV_SUB_NOUDF_U;
 }
 inline bool commutative(uint32_t op) {
     switch (op) {
-    case O_ADD: case O_MUL: case O_AND_BV: case O_OR_BV: case O_XOR_BV: case O_EQ: case O_DISTINCT:
-    case O_AND: case O_OR: case O_XOR: case O_ADD_NOOVFL: case O_MUL_NOOVFL:
-    case O_UMIN: case O_UMAX: case O_SMIN: case O_SMAX:
+    case MG_BV_ADD: case MG_BV_MUL: case MG_BV_AND: case MG_BV_OR: case MG_BV_XOR: case MG_BV_EQ: case MG_BV_NE:
+    case MG_BV_BAND: case MG_BV_BOR: case MG_BV_BXOR: case MG_BV_ADD_NOOVF_U: case MG_BV_MUL_NOOVF_U:
+    case MG_BV_UMIN: case MG_BV_UMAX: case MG_BV_SMIN: case MG_BV_SMAX:
         return true;
     default:
         return false;
@@ -56,10 +47,12 @@ inline bool commutative(uint32_t op) {
 // operand-swapped form (NONE: none)
 inline uint32_t swapped(uint32_t op) {
     switch (op) {
-    case O_ULT: return O_UGT; case O_UGT: return O_ULT; case O_ULE: return O_UGE; case O_UGE: return O_ULE;
-    case O_SLT: return O_SGT; case O_SGT: return O_SLT; case O_SLE: return O_SGE; case O_SGE: return O_SLE;
-    case O_SUB: return O_RSUB; case O_RSUB: return O_SUB; case O_CONCAT: return O_RCONCAT;
-    case O_RCONCAT: return O_CONCAT;
+    case MG_BV_ULT: return MG_BV_UGT; case MG_BV_UGT: return MG_BV_ULT;
+    case MG_BV_ULE: return MG_BV_UGE; case MG_BV_UGE: return MG_BV_ULE;
+    case MG_BV_SLT: return MG_BV_SGT; case MG_BV_SGT: return MG_BV_SLT;
+    case MG_BV_SLE: return MG_BV_SGE; case MG_BV_SGE: return MG_BV_SLE;
+    case MG_BV_SUB: return MG_BV_RSUB; case MG_BV_RSUB: return MG_BV_SUB;
+    case MG_BV_CONCAT: return MG_BV_RCONCAT; case MG_BV_RCONCAT: return MG_BV_CONCAT;
     default: return NONE;
     }
 }
@@ -101,7 +94,7 @@ struct Compiler {
     std::string err;
 
     uint32_t arg(uint32_t id, uint32_t k) const { return args[nodes[id].a0 + k]; }
-    bool leaf(uint32_t id) const { return nodes[id].op == O_VAR || nodes[id].op == O_CONST; }
+    bool leaf(uint32_t id) const { return nodes[id].op == MG_CC_VAR || nodes[id].op == MG_CC_CONST; }
 
     uint32_t make(uint32_t op, uint32_t width, uint32_t imm, const std::vector<uint32_t> &a) {
         Key k{op, width, imm, a};
@@ -160,25 +153,25 @@ struct Compiler {
             bool same = true;
             for (uint32_t k = 0; k < nd.n; ++k) { a[k] = fold_of[arg(x, k)]; same &= a[k] == arg(x, k); }
             uint32_t out = same ? x : make(nd.op, nd.width, nd.imm, a);
-            if (nd.op == O_ITE && nd.width > 1) {
+            if (nd.op == MG_BV_ITE && nd.width > 1) {
                 const uint32_t c = a[0], p = a[1], q = a[2];
                 const uint32_t cop = nodes[c].op;
-                const bool minmax = cop >= O_ULT && cop <= O_SGE;
-                if ((minmax || cop == O_EQ) && nodes[c].n == 2) {
+                const bool minmax = cop >= MG_BV_ULT && cop <= MG_BV_SGE;
+                if ((minmax || cop == MG_BV_EQ) && nodes[c].n == 2) {
                     const uint32_t cx = arg(c, 0), cy = arg(c, 1);
                     const bool fwd = cx == p && cy == q, rev = cy == p && cx == q;
                     if (fwd || rev) {
-                        if (cop == O_EQ) {
+                        if (cop == MG_BV_EQ) {
                             out = q;
                         } else {
                             // (lo, hi) op per compare: ult/ule -> (umin, umax), ugt/uge ->
                             // (umax, umin), slt/sle -> (smin, smax), sgt/sge -> (smax, smin)
                             uint32_t lo, hi;
                             switch (cop) {
-                            case O_ULT: case O_ULE: lo = O_UMIN; hi = O_UMAX; break;
-                            case O_UGT: case O_UGE: lo = O_UMAX; hi = O_UMIN; break;
-                            case O_SLT: case O_SLE: lo = O_SMIN; hi = O_SMAX; break;
-                            default: lo = O_SMAX; hi = O_SMIN; break;
+                            case MG_BV_ULT: case MG_BV_ULE: lo = MG_BV_UMIN; hi = MG_BV_UMAX; break;
+                            case MG_BV_UGT: case MG_BV_UGE: lo = MG_BV_UMAX; hi = MG_BV_UMIN; break;
+                            case MG_BV_SLT: case MG_BV_SLE: lo = MG_BV_SMIN; hi = MG_BV_SMAX; break;
+                            default: lo = MG_BV_SMAX; hi = MG_BV_SMIN; break;
                             }
                             out = make(fwd ? lo : hi, nd.width, 0, {cx, cy});
                         }
@@ -222,7 +215,7 @@ struct Compiler {
             if (it != vid.end()) { v.arg[k] = it->second; v.is_virt[k] = true; }
             else { v.arg[k] = c; v.is_virt[k] = false; }
         };
-        if ((nd.op == O_AND || nd.op == O_OR) && nd.n > 2) {
+        if ((nd.op == MG_BV_BAND || nd.op == MG_BV_BOR) && nd.n > 2) {
             Virt v{nd.op, 1, 0, 2, {0, 0, 0}, {false, false, false}};
             opnd(v, 0, arg(x, 0));
             for (uint32_t k = 1; k < nd.n; ++k) {
@@ -236,24 +229,24 @@ struct Compiler {
         }
         Virt v{nd.op, nd.width, 0, nd.n, {0, 0, 0}, {false, false, false}};
         if (nd.n > 3) { err = "operation with more than three operands"; return false; }
-        if ((nd.op == O_AND || nd.op == O_OR) && nd.n == 1) {
-            v.op = O_COPY;
+        if ((nd.op == MG_BV_BAND || nd.op == MG_BV_BOR) && nd.n == 1) {
+            v.op = MG_BV_COPY;
             v.width = 1;
-        } else if (nd.op == O_ZEXT && vid.count(arg(x, 0))) {
+        } else if (nd.op == MG_BV_ZEXT && vid.count(arg(x, 0))) {
             vid[x] = vid[arg(x, 0)];            // values are kept masked: the same instruction
             return true;
-        } else if (nd.op == O_EXTRACT) {
+        } else if (nd.op == MG_BV_EXTRACT) {
             v.imm = nd.imm;                      // low bit
-        } else if (nd.op == O_SEXT) {
+        } else if (nd.op == MG_BV_SEXT) {
             v.imm = nodes[arg(x, 0)].width;
-        } else if (nd.op == O_CONCAT) {
+        } else if (nd.op == MG_BV_CONCAT) {
             v.imm = nodes[arg(x, 1)].width;
         } else if (is_cmp(nd.op)) {
             v.width = 1;
             v.imm = nodes[arg(x, 0)].width;
-        } else if (nd.op == O_TAB) {
+        } else if (nd.op == MG_BV_TAB) {
             v.imm = nd.imm;
-        } else if (nd.op >= N_DEVICE_OPS) {
+        } else if (nd.op >= MG_BV_NUM_OPS) {
             err = "operation not evaluated on the device";
             return false;
         }
@@ -302,7 +295,7 @@ struct Compiler {
         std::vector<Virt> vs;
         std::unordered_map<uint32_t, uint32_t> vid;
         std::vector<uint32_t> conj;
-        if (nodes[root].op == O_AND) for (uint32_t k = 0; k < nodes[root].n; ++k) conj.push_back(arg(root, k));
+        if (nodes[root].op == MG_BV_BAND) for (uint32_t k = 0; k < nodes[root].n; ++k) conj.push_back(arg(root, k));
         else conj.push_back(root);
         bool have = false;
         uint32_t run = 0;
@@ -316,21 +309,21 @@ struct Compiler {
             else { cur = c; cur_virt = false; }
             if (!have) {
                 if (!cur_virt) {
-                    Virt v{O_COPY, nodes[c].width, 0, 1, {c, 0, 0}, {false, false, false}};
+                    Virt v{MG_BV_COPY, nodes[c].width, 0, 1, {c, 0, 0}, {false, false, false}};
                     vs.push_back(v);
                     cur = (uint32_t)vs.size() - 1;
                     cur_virt = true;
                 }
                 run = cur; run_virt = cur_virt; have = true;
             } else {
-                Virt v{O_AND, 1, 0, 2, {run, cur, 0}, {run_virt, cur_virt, false}};
+                Virt v{MG_BV_BAND, 1, 0, 2, {run, cur, 0}, {run_virt, cur_virt, false}};
                 vs.push_back(v);
                 run = (uint32_t)vs.size() - 1;
                 run_virt = true;
             }
         }
         const uint32_t n = (uint32_t)vs.size();
-        if (n > TILE_INSNS) { err = "program longer than one LDS tile"; return -1; }
+        if (n > MG_BV_TILE_INSNS) { err = "program longer than one LDS tile"; return -1; }
         // uses of each instruction's result
         std::vector<std::vector<std::pair<uint32_t, uint32_t>>> uses(n);
         for (uint32_t i = 0; i < n; ++i)
@@ -348,7 +341,7 @@ struct Compiler {
             needs[j] = need;
         }
         std::vector<uint32_t> free_slots;
-        for (int s = (int)MAX_SLOTS - 1; s >= 0; --s) free_slots.push_back((uint32_t)s);
+        for (int s = (int)MG_BV_MAX_SLOTS - 1; s >= 0; --s) free_slots.push_back((uint32_t)s);
         std::vector<std::vector<uint32_t>> expiring(n + 2);
         for (uint32_t i = 0; i < n; ++i) {
             for (uint32_t s : expiring[i]) free_slots.push_back(s);
@@ -370,11 +363,11 @@ struct Compiler {
                 if (v.is_virt[k]) {
                     const uint32_t j = v.arg[k];
                     const bool acc = j + 1 == i && (k == 0 || slot_of[j] == NONE);
-                    refs[k] = acc ? (REF_ACC << 30) : ((REF_SLOT << 30) | slot_of[j]);
+                    refs[k] = acc ? (MG_BV_REF_ACC << 30) : ((MG_BV_REF_SLOT << 30) | slot_of[j]);
                     is_acc[k] = acc;
                 } else {
                     const Node &lf = nodes[v.arg[k]];
-                    refs[k] = ((lf.op == O_CONST ? REF_CONST : REF_VAR) << 30) | lf.imm;
+                    refs[k] = ((lf.op == MG_CC_CONST ? MG_BV_REF_CONST : MG_BV_REF_VAR) << 30) | lf.imm;
                 }
             }
             uint32_t op = v.op;
@@ -390,8 +383,8 @@ struct Compiler {
             uint32_t *w = &out[(size_t)i * 4];
             w[0] = w0;
             for (uint32_t k = 0; k < v.nargs; ++k) w[1 + k] = refs[k];
-            if (v.op == O_EXTRACT || v.op == O_SEXT) w[2] = v.imm;
-            else if (v.op == O_CONCAT || v.op == O_RCONCAT || is_cmp(v.op) || v.op == O_TAB) w[3] = v.imm;
+            if (v.op == MG_BV_EXTRACT || v.op == MG_BV_SEXT) w[2] = v.imm;
+            else if (v.op == MG_BV_CONCAT || v.op == MG_BV_RCONCAT || is_cmp(v.op) || v.op == MG_BV_TAB) w[3] = v.imm;
         }
         return (int)n;
     }

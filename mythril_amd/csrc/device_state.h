@@ -11,6 +11,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "../../include/mythgpu.h"   // MG_FENT_NONE
+
 struct DevLanes {
     uint32_t n;          // lanes in the batch
     uint32_t N;          // row pitch in lanes (n rounded up to 64)
@@ -96,4 +98,3 @@ struct DevCounters {
 };
 
 #define MG_JRES_NONE 0xffffffffu
-#define MG_FENT_NONE 0xffffffffu

@@ -17,53 +17,19 @@
 #include "device_state.h"
 #include "keccak.cuh"
 #include "u256.cuh"
+#include "../../include/mythgpu.h"   // statuses, exception / escape reasons, lane flags
 
-// ---- constants shared with the host side (mythgpu.hip) ----------------------
 struct OpInfo {
     uint32_t gmin, gmax;   // support/opcodes.py:16-144 GAS
     uint32_t req;          // STACK[0]: items required by the svm precheck
     uint32_t valid;        // 0 -> disassembles to INVALID
 };
 
-#define ST_RUNNING 0u
-#define ST_STOP 1u
-#define ST_RETURN 2u
-#define ST_REVERT 3u
-#define ST_END 4u
-#define ST_DROPPED 5u
-#define ST_VMEXC 6u
-#define ST_HOOK 7u
-#define ST_ESCAPE 8u
-#define ST_DEPTH 9u
-#define ST_LOOP 10u
-
-#define EXC_UNDERFLOW 1u
-#define EXC_OVERFLOW 2u
-#define EXC_BADJUMP 3u
-#define EXC_INVALID 4u
-#define EXC_OOG 5u
-#define EXC_WRITEPROT 6u
-
-#define ESC_OPCODE 1u
-#define ESC_MEMORY 2u
-#define ESC_STORAGE 3u
-#define ESC_STACK 4u
-#define ESC_TRACE 5u
-#define ESC_RECORD 6u
-
-#define LANE_STATIC 1u
-#define LANE_CREATION 2u
-#define LANE_HOOK_ACK 4u
-#define LANE_STEP1 8u
-#define LANE_RETDATA 16384u
-
-#define MSTATE_GAS_LIMIT 1000000000ull
 #ifndef MG_K1_PF
 #define MG_K1_PF 0
 #endif
 #define RUN_MAX 64u   // longest straight-line run executed as one block
 static_assert(RUN_MAX <= 64u, "a run is read as one pre-decoded word per wave lane");
-#define STACK_LIMIT 1024u
 #define BIG_END (1ull << 32)
 #define HUGE_GAS (1ull << 62)
 
@@ -218,9 +184,9 @@ DEV int mem_extend(const U256 &start, const U256 &size, uint32_t &msize, uint64_
     if (nw == ow) return MX_OK;
     const uint64_t fee = (3u * nw + (nw * nw) / 512u) - (3u * ow + (ow * ow) / 512u);
     const uint64_t nmin = gmin + fee;
-    if (nmin > MSTATE_GAS_LIMIT) return MX_OOG;
+    if (nmin > MG_MSTATE_GAS_LIMIT) return MX_OOG;
     if (nw * 32u > mem_cap) {
-        if (later_min >= 0 && (nmin + (uint64_t)later_min > MSTATE_GAS_LIMIT ||
+        if (later_min >= 0 && (nmin + (uint64_t)later_min > MG_MSTATE_GAS_LIMIT ||
                                nmin + (uint64_t)later_min >= txlim))
             return MX_OOG;
         return MX_ESCAPE;
@@ -231,7 +197,7 @@ DEV int mem_extend(const U256 &start, const U256 &size, uint32_t &msize, uint64_
     return MX_OK;
 }
 
-DEV bool gas_oog(uint64_t gmin, uint64_t txlim) { return gmin > MSTATE_GAS_LIMIT || gmin >= txlim; }
+DEV bool gas_oog(uint64_t gmin, uint64_t txlim) { return gmin > MG_MSTATE_GAS_LIMIT || gmin >= txlim; }
 
 // Keccak-256 of memory [off, off+len) (off + len <= msize <= mem_cap).  With
 // rec != nullptr the input is also copied to the record payload at rec (one
@@ -387,7 +353,7 @@ struct LaneRegs {
     uint64_t gmin, gmax;
     uint32_t pc, sp, msize, depth;
     uint32_t n_sha3, n_exp;
-    uint32_t stop, sx;           // out: ST_RUNNING or the stop status and its aux word
+    uint32_t stop, sx;           // out: MG_RUNNING or the stop status and its aux word
     uint32_t step;               // instructions this launch executed before this one
     uint32_t fent;               // last JUMP / JUMPI landing on a function entry (L.fent)
 };
@@ -440,7 +406,7 @@ __device__ __forceinline__ void slow_step(LaneRegs &R, const StepEnv &E, uint32_
     const uint32_t sp = R.sp, pc = R.pc, msize0 = R.msize;
     uint32_t nmsize = R.msize, ndepth = R.depth, npc = pc + 1u, nfent = R.fent;
     uint64_t ngmin = R.gmin, ngmax = R.gmax;
-    uint32_t stop = ST_RUNNING, sx = 0;
+    uint32_t stop = MG_RUNNING, sx = 0;
     bool by_table = true;
     const U256 a = R.T0, b = R.T1;
     U256 c = u_zero(), res = u_zero();
@@ -450,13 +416,13 @@ __device__ __forceinline__ void slow_step(LaneRegs &R, const StepEnv &E, uint32_
     uint32_t rec_at = 0u, rec_new = 0u;     // function-manager record log (rec_cap > 0)
 
 #define STOPX(s_, x_) { stop = (s_); sx = (x_); break; }
-#define EXCX(k_) STOPX(ST_VMEXC, (k_))
-#define ESCX(r_) STOPX(ST_ESCAPE, op | ((r_) << 8))
+#define EXCX(k_) STOPX(MG_VMEXC, (k_))
+#define ESCX(r_) STOPX(MG_ESCAPE, op | ((r_) << 8))
 #define GASCOMMIT() if (by_table) { ngmin += gtab_min; ngmax += gtab_max; by_table = false; \
-                                    if (ngmin >= glim) EXCX(EXC_OOG) }
+                                    if (ngmin >= glim) EXCX(MG_EXC_OUT_OF_GAS) }
 #define MEMX(st_, sz_, later_) { const int mx_ = mem_extend((st_), (sz_), nmsize, ngmin, ngmax, \
                                                         L.mem_cap, (later_), txlim); \
-                                 if (mx_ == MX_OOG) EXCX(EXC_OOG) if (mx_ == MX_ESCAPE) ESCX(ESC_MEMORY) }
+                                 if (mx_ == MX_OOG) EXCX(MG_EXC_OUT_OF_GAS) if (mx_ == MX_ESCAPE) ESCX(MG_ESC_MEMORY) }
 #define ZEROFILL() if (nmsize > msize0) V.mzero(msize0, nmsize);
 #define JUMP_OK(idx_) ((idx_) != MG_JRES_NONE && \
                        ((E.sflag && (idx_) < E.sn) ? (E.s_pd[(idx_)].y & 0xffu) : (uint32_t)gops[(idx_)]) == 0x5bu)
@@ -466,16 +432,16 @@ __device__ __forceinline__ void slow_step(LaneRegs &R, const StepEnv &E, uint32_
     do {
         // svm.py:391-402 precheck; instructions.py:188-193 write protection;
         // then what the mutator really pops (ADDMOD, SSTORE pop more than `req`)
-        if (sp < req) EXCX(EXC_UNDERFLOW)
-        if ((op == 0x55u || (op >= 0xa0u && op <= 0xa4u)) && (E.flags & LANE_STATIC)) EXCX(EXC_WRITEPROT)
-        if (sp < npop) EXCX(EXC_UNDERFLOW)
+        if (sp < req) EXCX(MG_EXC_STACK_UNDERFLOW)
+        if ((op == 0x55u || (op >= 0xa0u && op <= 0xa4u)) && (E.flags & MG_LANE_STATIC)) EXCX(MG_EXC_WRITE_PROTECTION)
+        if (sp < npop) EXCX(MG_EXC_STACK_UNDERFLOW)
         if (npop >= 3u) c = V.stack(sp - 3u);
         bool tos_done = false;
         switch (kind) {
         case K_ALU:
             if (op == 0x0a && L.rec_cap) {
                 rec_at = L.rec_len[lane];
-                if (rec_at + MG_REC_HEADER + 16u > L.rec_cap) ESCX(ESC_RECORD)
+                if (rec_at + MG_REC_HEADER + 16u > L.rec_cap) ESCX(MG_ESC_RECORD)
             }
             res = alu(op, a, b, c);
             if (op == 0x0a) {
@@ -489,13 +455,13 @@ __device__ __forceinline__ void slow_step(LaneRegs &R, const StepEnv &E, uint32_
             break;
         case K_DUP: {                                       // (:322-331)
             const uint32_t k = op - 0x7fu;
-            if (sp < k) EXCX(EXC_UNDERFLOW)
+            if (sp < k) EXCX(MG_EXC_STACK_UNDERFLOW)
             res = k == 1u ? a : k == 2u ? b : V.stack(sp - k);
             break;
         }
         case K_SWAP: {                                      // (:333-343)
             const uint32_t k = op - 0x8fu;
-            if (sp < k + 1u) EXCX(EXC_UNDERFLOW)
+            if (sp < k + 1u) EXCX(MG_EXC_STACK_UNDERFLOW)
             if (k == 1u) {
                 GASCOMMIT()
                 R.T0 = b; R.T1 = a;
@@ -509,7 +475,7 @@ __device__ __forceinline__ void slow_step(LaneRegs &R, const StepEnv &E, uint32_
             break;
         }
         case K_RDCOPY:                                      // last_return_data None: pops only
-            if (E.flags & LANE_RETDATA) ESCX(ESC_OPCODE)
+            if (E.flags & MG_LANE_RETDATA) ESCX(MG_ESC_OPCODE)
             break;
         case K_LOG: case K_POP: case K_JUMPDEST:
             break;                                          // pops only / no-op
@@ -522,27 +488,27 @@ __device__ __forceinline__ void slow_step(LaneRegs &R, const StepEnv &E, uint32_
             case 0x3a: res = V.env(4); break;               // GASPRICE
             case 0x36: res = u_small(L.calldata_len[lane]); break;
             case 0x38: res = u_small(C.n_bytes); break;     // CODESIZE
-            case 0x45: res = u_small(MSTATE_GAS_LIMIT); break;
+            case 0x45: res = u_small(MG_MSTATE_GAS_LIMIT); break;
             case 0x58: res = u_small(a32[C.addr_off + pc]); break;
             case 0x59: res = u_small(msize0); break;
             default:                                        // RETURNDATASIZE
-                if (E.flags & LANE_RETDATA) ESCX(ESC_OPCODE)
+                if (E.flags & MG_LANE_RETDATA) ESCX(MG_ESC_OPCODE)
                 res = u_zero();
                 break;
             }
             break;
-        case K_STOP: STOPX(ST_STOP, 0u)
+        case K_STOP: STOPX(MG_HALT_STOP, 0u)
         case K_SHA3: {  // own gas first, then mem_extend (instructions.py:1013-1051)
             by_table = false;
             const bool big = (b.w[2] | b.w[3] | b.w[4] | b.w[5] | b.w[6] | b.w[7]) != 0u;
             const uint64_t blen = (uint64_t)b.w[0] | ((uint64_t)b.w[1] << 32);
             const uint64_t g = (big || blen > BIG_END) ? HUGE_GAS : 30ull + 6ull * ((blen + 31ull) >> 5);
             ngmin += g; ngmax += g;
-            if (ngmin >= glim) EXCX(EXC_OOG)
+            if (ngmin >= glim) EXCX(MG_EXC_OUT_OF_GAS)
             MEMX(a, b, -1)
             if (b.w[0] != 0u && L.rec_cap) {
                 rec_at = L.rec_len[lane];
-                if ((uint64_t)rec_at + MG_REC_HEADER + ((b.w[0] + 3u) >> 2) > L.rec_cap) ESCX(ESC_RECORD)
+                if ((uint64_t)rec_at + MG_REC_HEADER + ((b.w[0] + 3u) >> 2) > L.rec_cap) ESCX(MG_ESC_RECORD)
             }
             ZEROFILL()
             if (b.w[0] == 0u) {  // get_empty_keccak_hash (keccak_function_manager.py:87-93)
@@ -655,7 +621,7 @@ __device__ __forceinline__ void slow_step(LaneRegs &R, const StepEnv &E, uint32_
         case K_CODECOPY: {  // extends even for size 0; copy stops at the end of code
             // creation transaction (symbolic calldata): an offset at or past the end
             // of the code copies constructor arguments (instructions.py:1089-1098)
-            if ((E.flags & LANE_CREATION) && !(u_fits32(b) && b.w[0] < C.n_bytes)) ESCX(ESC_OPCODE)
+            if ((E.flags & MG_LANE_CREATION) && !(u_fits32(b) && b.w[0] < C.n_bytes)) ESCX(MG_ESC_OPCODE)
             MEMX(a, c, (int64_t)gtab_min)
             GASCOMMIT()
             ZEROFILL()
@@ -698,7 +664,7 @@ __device__ __forceinline__ void slow_step(LaneRegs &R, const StepEnv &E, uint32_
             uint32_t slot = cnt;
             for (uint32_t s = 0; s < cnt; ++s)
                 if (u_eq(ld_word(gv(L.storage), V.row(s) * 2), a)) { slot = s; break; }
-            if (slot == cnt && cnt >= L.storage_cap) ESCX(ESC_STORAGE)
+            if (slot == cnt && cnt >= L.storage_cap) ESCX(MG_ESC_STORAGE)
             GASCOMMIT()
             if (slot == cnt) {
                 st_word(gv(L.storage), V.row(slot) * 2, a);
@@ -711,7 +677,7 @@ __device__ __forceinline__ void slow_step(LaneRegs &R, const StepEnv &E, uint32_
             by_table = false;
             uint32_t idx = MG_JRES_NONE;
             if (u_fits32(a) && a.w[0] < C.n_jres) idx = a32[C.jres_off + a.w[0]];
-            if (!JUMP_OK(idx)) EXCX(EXC_BADJUMP)
+            if (!JUMP_OK(idx)) EXCX(MG_EXC_INVALID_JUMP)
             ngmin += 8u; ngmax += 8u; npc = idx;
             if (FENT_AT(idx)) nfent = idx;
             break;
@@ -724,30 +690,30 @@ __device__ __forceinline__ void slow_step(LaneRegs &R, const StepEnv &E, uint32_
             } else {
                 uint32_t idx = MG_JRES_NONE;
                 if (u_fits32(a) && a.w[0] < C.n_jres) idx = a32[C.jres_off + a.w[0]];
-                if (!JUMP_OK(idx)) STOPX(ST_DROPPED, 0u)
+                if (!JUMP_OK(idx)) STOPX(MG_HALT_DROPPED, 0u)
                 ngmin += 10u; ngmax += 10u; ++ndepth; npc = idx;
                 if (FENT_AT(idx)) nfent = idx;
             }
             break;
         }
-        case K_BEGINSUB: EXCX(EXC_OOG)
+        case K_BEGINSUB: EXCX(MG_EXC_OUT_OF_GAS)
         case K_RETURN:  // (:1857-1874)
             MEMX(a, b, 0)
-            if (ngmin >= glim) EXCX(EXC_OOG)
+            if (ngmin >= glim) EXCX(MG_EXC_OUT_OF_GAS)
             L.ret_offset[lane] = a.w[0]; L.ret_len[lane] = b.w[0];
-            STOPX(ST_RETURN, 0u)
+            STOPX(MG_HALT_RETURN, 0u)
         case K_REVERT:  // no memory extension (:1899-1934)
             L.ret_offset[lane] = a.w[0]; L.ret_len[lane] = b.w[0];
-            STOPX(ST_REVERT, 0u)
-        case K_INVALID: EXCX(EXC_INVALID)
-        default: ESCX(ESC_OPCODE)
+            STOPX(MG_HALT_REVERT, 0u)
+        case K_INVALID: EXCX(MG_EXC_INVALID_INSTRUCTION)
+        default: ESCX(MG_ESC_OPCODE)
         }
-        if (stop != ST_RUNNING) break;
+        if (stop != MG_RUNNING) break;
         if (tos_done) { GASCOMMIT() break; }
         // new top-of-stack registers from the pops / push of this opcode
         if (push) {   // MachineStack.append: overflow check precedes the write
-            if (nsp + 1u > STACK_LIMIT) EXCX(EXC_OVERFLOW)
-            if (nsp + 1u > L.stack_cap) ESCX(ESC_STACK)
+            if (nsp + 1u > MG_STACK_LIMIT) EXCX(MG_EXC_STACK_OVERFLOW)
+            if (nsp + 1u > L.stack_cap) ESCX(MG_ESC_STACK)
             GASCOMMIT()
             if (npop == 0u) {            // T1 moves below the register window
                 if (sp >= 2u && !E.tosmem) V.set_stack(sp - 2u, b);
@@ -777,7 +743,7 @@ __device__ __forceinline__ void slow_step(LaneRegs &R, const StepEnv &E, uint32_
 #undef FENT_AT
     R.stop = stop;
     R.sx = sx;
-    if (stop == ST_RUNNING) {
+    if (stop == MG_RUNNING) {
         if (rec_new) L.rec_len[lane] = rec_new;
         R.pc = npc; R.sp = nsp + (push ? 1u : 0u);
         R.msize = nmsize; R.depth = ndepth; R.gmin = ngmin; R.gmax = ngmax; R.fent = nfent;
@@ -894,6 +860,15 @@ __device__ __forceinline__ void reset_lane(const DevLanes &L, const DevResetImag
 __device__ uint32_t g_k1_clk[4096u * CLK_BINS];
 #endif
 
+// k_lane_step's launch word `lpw_flags` (internal: packed by launch_step)
+#define K1_LPW_MASK 0xffu        // bits 0..7: lanes per wave
+#define K1_REG_RUNS 0x100u       // register-form runs only (MG_K1_RUNS=reg, for A/B runs against
+                                 // the LDS-resident form)
+#define K1_PUSH_LDS 0x200u       // the push immediates are staged in LDS too (otherwise read from
+                                 // the code arena at wave-uniform addresses)
+#define K1_MW_SHIFT 16           // bits 16..23: LDS memory window per lane in 32-byte words
+#define K1_MW_MASK 0xffu
+
 template <bool kLoop>
 __global__ __launch_bounds__(LANE_BLOCK) void k_lane_step(DevLanes L, const DevCode *__restrict__ codes,
                                                           const uint8_t *__restrict__ a8,
@@ -906,15 +881,10 @@ __global__ __launch_bounds__(LANE_BLOCK) void k_lane_step(DevLanes L, const DevC
                                                           uint32_t win, uint32_t pd_cap, uint32_t jr_cap,
                                                           uint32_t horizon, uint32_t loop_bound,
                                                           DevResetImage R, uint32_t lpw_flags) {
-    // lpw_flags: lanes per wave in bits 0..7; bit 8 = register-form runs only
-    // (MG_K1_RUNS=reg, for A/B runs against the LDS-resident form); bit 9 = the
-    // push immediates are staged in LDS too (otherwise read from the code arena
-    // at wave-uniform addresses)
-    const uint32_t lpw = lpw_flags & 0xffu;
-    const bool lds_runs_on = (lpw_flags & 0x100u) == 0u;
-    const bool push_lds = (lpw_flags & 0x200u) != 0u;
-    // bits 16..23: LDS memory window per lane in 32-byte words
-    const uint32_t mw = ((lpw_flags >> 16) & 0xffu) * 8u;
+    const uint32_t lpw = lpw_flags & K1_LPW_MASK;
+    const bool lds_runs_on = (lpw_flags & K1_REG_RUNS) == 0u;
+    const bool push_lds = (lpw_flags & K1_PUSH_LDS) != 0u;
+    const uint32_t mw = ((lpw_flags >> K1_MW_SHIFT) & K1_MW_MASK) * 8u;
     // Dynamic LDS: [stack window: win x 2 x lanes-per-block x 16 B]
     //              [memory window: mw x lanes-per-block x 4 B]
     //              [pre-decoded code: pd_cap x 16 B: decode x, y | run table z, w]
@@ -956,7 +926,7 @@ __global__ __launch_bounds__(LANE_BLOCK) void k_lane_step(DevLanes L, const DevC
     // mg_run_batches: re-initialise the lane from the resident image first (the
     // reads below see this thread's own stores)
     if (R.pc != nullptr && in_range) reset_lane(L, R, lane);
-    uint32_t status = in_range ? L.status[lane] : ST_STOP;
+    uint32_t status = in_range ? L.status[lane] : MG_HALT_STOP;
     const uint32_t my_code = in_range ? L.code_id[lane] : 0u;
     for (uint32_t i = threadIdx.x; i < 256u; i += blockDim.x) s_dec[i] = kDec[i];
     if (prof)
@@ -964,7 +934,7 @@ __global__ __launch_bounds__(LANE_BLOCK) void k_lane_step(DevLanes L, const DevC
     if (threadIdx.x == 0) s_code = 0xffffffffu;
     if ((threadIdx.x & 63u) < 2u) s_kc[(threadIdx.x >> 6) * KC_WAVE + KC_E * 24u + (threadIdx.x & 63u)] = 0u;
     __syncthreads();
-    if (status == ST_RUNNING) s_code = my_code;      // any running lane's code (benign race)
+    if (status == MG_RUNNING) s_code = my_code;      // any running lane's code (benign race)
     __syncthreads();
 #ifdef MG_K1_CLOCKS
     __shared__ uint32_t s_clk[LANE_BLOCK / 64u][CLK_BINS];
@@ -986,7 +956,7 @@ __global__ __launch_bounds__(LANE_BLOCK) void k_lane_step(DevLanes L, const DevC
 #define CLK_MARK(next_) do { } while (0)
 #endif
     const uint32_t bcode = s_code;
-    const bool mixed = __syncthreads_or(status == ST_RUNNING && my_code != bcode);
+    const bool mixed = __syncthreads_or(status == MG_RUNNING && my_code != bcode);
     bool staged = false, jstaged = false;
     uint32_t ns_b = 0u, sn_b = 0u, jn_b = 0u, push_b = 0u;
     if (bcode != 0xffffffffu && !mixed) {
@@ -1028,8 +998,8 @@ __global__ __launch_bounds__(LANE_BLOCK) void k_lane_step(DevLanes L, const DevC
     }
     uint32_t executed = 0;
     // symbolic and taint lanes (MG_LANE_SYMBOLIC, MG_LANE_TAINT) are k_sym_step's: counted as running, untouched
-    const bool sym_lane = in_range && status == ST_RUNNING && (L.flags[lane] & (16u | 2048u)) != 0u;
-    const bool run0 = status == ST_RUNNING && !sym_lane;
+    const bool sym_lane = in_range && status == MG_RUNNING && (L.flags[lane] & (16u | 2048u)) != 0u;
+    const bool run0 = status == MG_RUNNING && !sym_lane;
     // block-uniform facts in scalar registers
     const uint32_t sflag = __builtin_amdgcn_readfirstlane(staged ? 1u : 0u);
     const uint32_t jflag = __builtin_amdgcn_readfirstlane(jstaged ? 1u : 0u);
@@ -1040,7 +1010,7 @@ __global__ __launch_bounds__(LANE_BLOCK) void k_lane_step(DevLanes L, const DevC
     const uint32_t psflag = (staged && push_lds) ? 1u : 0u;
     // push immediate of instruction i of the staged code (wave-uniform i in runs)
 #define PUSH_IMM(i_) (psflag ? ld_word((const l_u4 *)s_push, (i_)) : ld_word(gv(a32 + bpush), (i_)))
-    const uint32_t stack_lim = L.stack_cap < STACK_LIMIT ? L.stack_cap : STACK_LIMIT;
+    const uint32_t stack_lim = L.stack_cap < MG_STACK_LIMIT ? L.stack_cap : MG_STACK_LIMIT;
 
     // ---- per-lane machine state (registers) ----
     const LaneView V{L, lane, s_win, win, tid, lanes_pb, s_mw, mw};
@@ -1059,7 +1029,7 @@ __global__ __launch_bounds__(LANE_BLOCK) void k_lane_step(DevLanes L, const DevC
         flags = L.flags[lane];
         txlim = L.gas_limit[lane];
         // accumulate_gas OOG test (instructions.py:162-176): min > 1e9 or min >= tx gas limit
-        glim = txlim < MSTATE_GAS_LIMIT + 1ull ? txlim : MSTATE_GAS_LIMIT + 1ull;
+        glim = txlim < MG_MSTATE_GAS_LIMIT + 1ull ? txlim : MG_MSTATE_GAS_LIMIT + 1ull;
         pc = L.pc[lane]; sp = L.sp[lane]; msize = L.msize[lane]; depth = L.depth[lane];
         fent = L.fent[lane];
         if (loop_on) tlen = L.trace_len[lane];
@@ -1070,11 +1040,11 @@ __global__ __launch_bounds__(LANE_BLOCK) void k_lane_step(DevLanes L, const DevC
         if (sp >= 2u) T1 = V.stack(sp - 2u);
         live = true;
     }
-    const bool creation = (flags & LANE_CREATION) != 0u;
+    const bool creation = (flags & MG_LANE_CREATION) != 0u;
     // host hook protocol: HOOK_ACK lets the first instruction of this call run past
     // its hook bit; STEP1 caps the lane at one instruction (post-hooks)
-    const bool hook_ack = (flags & LANE_HOOK_ACK) != 0u;
-    uint32_t lane_max = (flags & LANE_STEP1) ? min(max_steps, 1u) : max_steps;
+    const bool hook_ack = (flags & MG_LANE_HOOK_ACK) != 0u;
+    uint32_t lane_max = (flags & MG_LANE_STEP1) ? min(max_steps, 1u) : max_steps;
     // step horizon (mg_step_until): the lane pauses once its cumulative steps reach it
     if (horizon && run0) {
         const uint32_t s0 = L.steps[lane];
@@ -1126,22 +1096,22 @@ __global__ __launch_bounds__(LANE_BLOCK) void k_lane_step(DevLanes L, const DevC
                                             creation ? 1u : 0u);                          \
             tlen = (uint32_t)tr_;                                                         \
             const uint32_t res_ = (uint32_t)(tr_ >> 60);                                  \
-            if (res_ == 1u) { status = ST_LOOP; aux = (uint32_t)(tr_ >> 32) & 0x0fffffffu; \
+            if (res_ == 1u) { status = MG_LOOP_BOUND; aux = (uint32_t)(tr_ >> 32) & 0x0fffffffu; \
                               live = false; lstop_ = true; }                              \
-            else if (res_ == 2u) { status = ST_ESCAPE; aux = o_ | (ESC_TRACE << 8);        \
+            else if (res_ == 2u) { status = MG_ESCAPE; aux = o_ | (MG_ESC_TRACE << 8);        \
                                    live = false; lstop_ = true; }                         \
         }                                                                                 \
         /* one test for the common case: bits 29/30 pre-decode "escape or END"  */      \
         /* and "escapes in a creation transaction" (CALLDATA*, CODESIZE/COPY)    */      \
         if (!lstop_ && (hk_ || (pd.y & PD_SPECIAL) || executed >= lane_max ||             \
             (max_depth != 0u && depth >= max_depth) || (creation && (pd.y & PD_CREATION)))) { \
-            uint32_t st_ = ST_RUNNING;                                                    \
-            if (max_depth != 0u && depth >= max_depth) st_ = ST_DEPTH;                    \
-            else if (k_ == K_END) st_ = ST_END;                                           \
-            else if (hk_) { st_ = ST_HOOK; aux = o_; }                                    \
+            uint32_t st_ = MG_RUNNING;                                                    \
+            if (max_depth != 0u && depth >= max_depth) st_ = MG_DEPTH;                    \
+            else if (k_ == K_END) st_ = MG_HALT_END;                                           \
+            else if (hk_) { st_ = MG_HOOK; aux = o_; }                                    \
             else if (executed >= lane_max) live = false;                                  \
-            else { st_ = ST_ESCAPE; aux = o_ | (ESC_OPCODE << 8); }                       \
-            if (st_ != ST_RUNNING) { status = st_; live = false; }                        \
+            else { st_ = MG_ESCAPE; aux = o_ | (MG_ESC_OPCODE << 8); }                       \
+            if (st_ != MG_RUNNING) { status = st_; live = false; }                        \
         }                                                                                 \
     } while (0)
 
@@ -1451,7 +1421,7 @@ __global__ __launch_bounds__(LANE_BLOCK) void k_lane_step(DevLanes L, const DevC
             }
             break;
         case K_ENV:
-            ok = gas_ok && sp + 1u <= stack_lim && !(op == 0x3du && (flags & LANE_RETDATA));
+            ok = gas_ok && sp + 1u <= stack_lim && !(op == 0x3du && (flags & MG_LANE_RETDATA));
             if (ok) {
                 U256 r;
                 switch (op) {
@@ -1462,7 +1432,7 @@ __global__ __launch_bounds__(LANE_BLOCK) void k_lane_step(DevLanes L, const DevC
                 case 0x3a: r = V.env(4); break;                 // GASPRICE
                 case 0x36: r = u_small(L.calldata_len[lane]); break;
                 case 0x38: r = u_small(C.n_bytes); break;       // CODESIZE
-                case 0x45: r = u_small(MSTATE_GAS_LIMIT); break;
+                case 0x45: r = u_small(MG_MSTATE_GAS_LIMIT); break;
                 case 0x58: r = u_small(a32[C.addr_off + pc]); break;
                 case 0x59: r = u_small(msize); break;
                 default: r = u_zero(); break;                   // RETURNDATASIZE
@@ -1504,10 +1474,10 @@ __global__ __launch_bounds__(LANE_BLOCK) void k_lane_step(DevLanes L, const DevC
             LaneRegs R{T0, T1, gmin, gmax, pc, sp, msize, depth, n_sha3, n_exp, 0u, 0u, executed - 1u, fent};
             slow_step(R, E, uk, ux);
             n_sha3 = R.n_sha3; n_exp = R.n_exp;
-            if (R.stop != ST_RUNNING) {
+            if (R.stop != MG_RUNNING) {
                 status = R.stop;
                 aux = R.sx;
-                if (R.stop == ST_ESCAPE) --executed;
+                if (R.stop == MG_ESCAPE) --executed;
                 live = false;
             } else {
                 T0 = R.T0; T1 = R.T1; gmin = R.gmin; gmax = R.gmax;
@@ -1540,7 +1510,7 @@ __global__ __launch_bounds__(LANE_BLOCK) void k_lane_step(DevLanes L, const DevC
         L.fent[lane] = fent;
         if (loop_on) L.trace_len[lane] = tlen;
         // HOOK_ACK covers one instruction: consumed once the lane has executed
-        if (hook_ack && executed > 0u) L.flags[lane] = flags & ~LANE_HOOK_ACK;
+        if (hook_ack && executed > 0u) L.flags[lane] = flags & ~MG_LANE_HOOK_ACK;
         L.steps[lane] += executed;
         if (n_sha3) L.sha3_count[lane] += n_sha3;
         if (n_exp) L.exp_count[lane] += n_exp;
@@ -1573,9 +1543,9 @@ __global__ __launch_bounds__(LANE_BLOCK) void k_lane_step(DevLanes L, const DevC
         __shared__ unsigned long long s_ctr[LANE_BLOCK / 64u][5];
         unsigned long long s = executed;
         for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-        const uint64_t b_run = __ballot(in_range && status == ST_RUNNING);
-        const uint64_t b_hook = __ballot(in_range && status == ST_HOOK);
-        const uint64_t b_esc = __ballot(in_range && status == ST_ESCAPE);
+        const uint64_t b_run = __ballot(in_range && status == MG_RUNNING);
+        const uint64_t b_hook = __ballot(in_range && status == MG_HOOK);
+        const uint64_t b_esc = __ballot(in_range && status == MG_ESCAPE);
         const uint64_t b_all = __ballot(in_range);
         const uint32_t w = threadIdx.x >> 6;
         if ((threadIdx.x & 63u) == 0u) {

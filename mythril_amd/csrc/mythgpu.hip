@@ -870,7 +870,7 @@ extern "C" int mg_sym_alloc(mg_ctx *ctx, uint32_t node_cap, uint32_t const_cap) 
     if (!ctx) return MG_EINVAL;
     if (!ctx->have_lanes) return set_err(ctx, MG_ESTATE, "mg_sym_alloc before mg_lanes_alloc");
     if (ctx->S.node) return set_err(ctx, MG_ESTATE, "mg_sym_alloc: already allocated for this batch");
-    if (node_cap == 0u || const_cap == 0u || node_cap >= SYM_CONST || const_cap >= SYM_CONST)
+    if (node_cap == 0u || const_cap == 0u || node_cap >= MG_SYM_CONST || const_cap >= MG_SYM_CONST)
         return set_err(ctx, MG_EINVAL, "mg_sym_alloc: bad capacities");
     HIPX(ctx, hipSetDevice(ctx->device));
     DevSym S{};
@@ -992,11 +992,16 @@ extern "C" int mg_taint_alloc(mg_ctx *ctx, uint32_t obj_cap) {
 extern "C" int mg_taint_program(mg_ctx *ctx, const uint32_t actions[256]) {
     if (!ctx || !actions) return MG_EINVAL;
     HIPX(ctx, hipSetDevice(ctx->device));
+    const uint32_t field = MG_TAINT_FIELD(~0u, 0);
+    const uint32_t known = MG_TAINT_POST | MG_TAINT_EXPCOND | MG_TAINT_YCLASS | MG_TAINT_IFLANE |
+                           field << MG_TAINT_PRE_SHIFT | field << MG_TAINT_SINK_SHIFT | field << MG_TAINT_YIELD_SHIFT |
+                           field << MG_TAINT_DEFER_SHIFT | field << MG_TAINT_IFSYM_SHIFT;
     for (int k = 0; k < 256; ++k) {
         const uint32_t a = actions[k];
-        if (a & ~0x1ffff7fu) return set_err(ctx, MG_EINVAL, "taint action %#x of opcode %#x: unknown bits", a, k);
-        if ((a & 15u) > 7u || ((a >> 8) & 15u) > 7u || ((a >> 12) & 15u) > 7u || ((a >> 16) & 15u) > 3u ||
-            ((a >> 20) & 15u) > 7u)
+        if (a & ~known) return set_err(ctx, MG_EINVAL, "taint action %#x of opcode %#x: unknown bits", a, k);
+        if (MG_TAINT_FIELD(a, MG_TAINT_PRE_SHIFT) > 7u || MG_TAINT_FIELD(a, MG_TAINT_SINK_SHIFT) > 7u ||
+            MG_TAINT_FIELD(a, MG_TAINT_YIELD_SHIFT) > 7u || MG_TAINT_FIELD(a, MG_TAINT_DEFER_SHIFT) > 3u ||
+            MG_TAINT_FIELD(a, MG_TAINT_IFSYM_SHIFT) > 7u)
             return set_err(ctx, MG_EINVAL, "taint action %#x of opcode %#x: operand out of range", a, k);
     }
     int rc;
@@ -1045,7 +1050,7 @@ extern "C" int mg_taint_upload(mg_ctx *ctx, const mg_taint_soa *h, uint32_t firs
     HIPX(ctx, hipSetDevice(ctx->device));
     for (uint32_t i = 0; i < n; ++i) {
         if (h->n_obj[i] > h->obj_cap || h->n_fixed[i] < MG_TAINT_OBJ0 || h->n_fixed[i] > h->n_obj[i] ||
-            h->n_atoms[i] > 64u)
+            h->n_atoms[i] > MG_TAINT_MAX_ATOMS)
             return set_err(ctx, MG_EINVAL, "lane %u: taint counts outside its capacities", first + i);
         // slots above the lane's sp may hold stale handles (never read before a push
         // writes them); every handle must index the object table
@@ -1247,7 +1252,7 @@ static LdsPlan lds_plan(const mg_ctx *ctx) {
 // read per launch so one process can alternate the two forms)
 static uint32_t k1_flags() {
     const char *r = getenv("MG_K1_RUNS");
-    return (r && std::string(r) == "reg") ? 0x100u : 0u;
+    return (r && std::string(r) == "reg") ? K1_REG_RUNS : 0u;
 }
 
 // plan / kflags: a caller launching many batches computes the LDS plan and the
@@ -1283,8 +1288,8 @@ static int launch_step(mg_ctx *ctx, const uint64_t hook_mask[4], uint32_t max_st
                        ctx->d_codes, ctx->d_a8, ctx->d_a32, ctx->d_cov, ctx->cfg.coverage ? 1u : 0u, m[0], m[1],
                        m[2], m[3], max_steps, max_depth, ctr, prof, P.win, P.pd_cap, P.jr_cap, horizon,
                        loop_bound, reset ? *reset : DevResetImage{},
-                       ctx->lpw | (kflags >= 0 ? (uint32_t)kflags : k1_flags()) | (P.push_lds ? 0x200u : 0u) |
-                       (P.mw32 << 16));
+                       ctx->lpw | (kflags >= 0 ? (uint32_t)kflags : k1_flags()) | (P.push_lds ? K1_PUSH_LDS : 0u) |
+                       (P.mw32 << K1_MW_SHIFT));
     HIPX(ctx, hipGetLastError());
     // symbolic and taint lanes: the concrete stepper left them untouched (counted as running)
     // (a profiling pass counts their opcodes into the same histogram)

@@ -1,6 +1,6 @@
 // sym_step.cuh — symbolic lanes: the expression arena.
 //
-// A lane flagged LANE_SYMBOLIC carries symbolic stack words: every stack slot has
+// A lane flagged MG_LANE_SYMBOLIC carries symbolic stack words: every stack slot has
 // a tag (0 = concrete value in the stack row, else 1 + the index of the arena
 // node that defines it).  Sources are symbolic calldata (CALLDATALOAD /
 // CALLDATASIZE of a SymbolicCalldata, state/calldata.py:214-262) and symbolic
@@ -29,19 +29,6 @@
 // round trip.
 #pragma once
 
-#define ST_FORK 11u
-#define ESC_SYMBOLIC 7u
-#define ESC_ARENA 8u
-#define LANE_SYMBOLIC 16u
-#define LANE_SYMCD 32u
-#define LANE_SYMENV_SHIFT 6u
-#define SYM_CDLOAD 1u
-#define SYM_CDSIZE 2u
-#define SYM_ENV 3u
-#define SYM_BIN 4u
-#define SYM_UN 5u
-#define SYM_CONST 0x80000000u
-
 DEV uint32_t sym_tag(const DevSym &S, size_t N, uint32_t lane, uint32_t slot) {
     return S.stag[(size_t)slot * N + lane];
 }
@@ -57,7 +44,7 @@ DEV bool sym_ref(const DevSym &S, size_t N, uint32_t lane, uint32_t tag, const U
     if (tag) { ref = tag - 1u; return true; }
     if (nc >= S.const_cap) return false;
     st_word(gv(S.cval), (size_t)nc * N + lane, v);
-    ref = SYM_CONST | nc;
+    ref = MG_SYM_CONST | nc;
     ++nc;
     return true;
 }
@@ -72,23 +59,7 @@ DEV bool sym_node_push(const DevSym &S, size_t N, uint32_t lane, uint32_t kind_w
 }
 
 // ---- symbolic memory, storage and SHA3 (ABI v7) ----------------------------------
-#define LANE_SYMSTORE 4096u
-#define LANE_MEMTAG 8192u
-#define LANE_SYMBAL 32768u
-#define LANE_SYMRDS 65536u
-#define LANE_BALANCE 131072u
-#define LANE_SYMBLOCK 262144u
-#define SYM_SLOAD 6u
-#define SYM_KECCAK 7u
-#define SYM_EXTRACT 8u
-#define SYM_CONCAT 9u
-#define SYM_TERM 10u
 #define SYM_NONE 0xffffffffu
-#define SYM_CDBYTE 12u
-#define SYM_CDBYTEX 13u
-#define SYM_MSTOREK 14u
-#define SYM_MLOADK 15u
-#define SYM_BALANCE 16u
 // A tagged word the host can only decode to a symbolic term: a fresh calldata word
 // or size, an environment word, a keccak of symbolic data.  Any other node (an
 // ALU result such as x - x, an MLOADK of a word stored concretely, a BALANCE of a
@@ -98,7 +69,7 @@ DEV bool sym_node_push(const DevSym &S, size_t N, uint32_t lane, uint32_t kind_w
 DEV bool sym_never_const(const DevSym &S, size_t N, uint32_t lane, uint32_t tag) {
     if (!tag) return false;
     const uint32_t kind = S.node[(size_t)(tag - 1u) * N + lane].x & 0xffu;
-    return kind == SYM_CDLOAD || kind == SYM_CDSIZE || kind == SYM_ENV || kind == SYM_KECCAK;
+    return kind == MG_SYM_CDLOAD || kind == MG_SYM_CDSIZE || kind == MG_SYM_ENV || kind == MG_SYM_KECCAK;
 }
 
 DEV uint32_t mtag_at(const DevSym &S, size_t N, uint32_t lane, uint32_t off) { return S.mtag[(size_t)off * N + lane]; }
@@ -131,19 +102,19 @@ __device__ __noinline__ bool sym_same(const uint4 *node, const uint4 *cval, size
     while (top) {
         const uint32_t b = st[--top], a = st[--top];
         if (a == b) continue;
-        const bool ca = (a & SYM_CONST) != 0u, cb = (b & SYM_CONST) != 0u;
+        const bool ca = (a & MG_SYM_CONST) != 0u, cb = (b & MG_SYM_CONST) != 0u;
         if (ca || cb) {
             if (!(ca && cb)) return false;
-            if (!u_eq(ld_word(gv(cval), (size_t)(a & ~SYM_CONST) * N + lane),
-                      ld_word(gv(cval), (size_t)(b & ~SYM_CONST) * N + lane)))
+            if (!u_eq(ld_word(gv(cval), (size_t)(a & ~MG_SYM_CONST) * N + lane),
+                      ld_word(gv(cval), (size_t)(b & ~MG_SYM_CONST) * N + lane)))
                 return false;
             continue;
         }
         const uint4 na = node[(size_t)a * N + lane], nb = node[(size_t)b * N + lane];
         if (na.x != nb.x || na.w != nb.w) return false;
         const uint32_t kind = na.x & 0xffu;
-        const bool yref = kind != SYM_CDSIZE && kind != SYM_ENV && kind != SYM_TERM;
-        const bool zref = kind == SYM_BIN || kind == SYM_CONCAT;
+        const bool yref = kind != MG_SYM_CDSIZE && kind != MG_SYM_ENV && kind != MG_SYM_TERM;
+        const bool zref = kind == MG_SYM_BIN || kind == MG_SYM_CONCAT;
         if (!yref && na.y != nb.y) return false;
         if (!zref && na.z != nb.z) return false;      // SLOAD: the chain length
         if (top + 4 > 32) return false;
@@ -182,7 +153,7 @@ __device__ __noinline__ bool sym_mem_ref(const DevSym S, const uint32_t *mem, si
             }
             if (nc >= S.const_cap) return false;
             st_word(gv(S.cval), (size_t)nc * N + lane, v);
-            part = SYM_CONST | nc;
+            part = MG_SYM_CONST | nc;
             ++nc;
             pw = 8u * run;
         } else {
@@ -204,7 +175,7 @@ __device__ __noinline__ bool sym_mem_ref(const DevSym S, const uint32_t *mem, si
             } else {
                 const uint32_t hi = 255u - 8u * j0, lo = 248u - 8u * (j0 + run - 1u);
                 uint32_t et;
-                if (!sym_node_push(S, N, lane, SYM_EXTRACT | ((hi - lo + 1u) << 8), t, 0u, (hi << 16) | lo, nn, et))
+                if (!sym_node_push(S, N, lane, MG_SYM_EXTRACT | ((hi - lo + 1u) << 8), t, 0u, (hi << 16) | lo, nn, et))
                     return false;
                 part = et - 1u;
                 pw = hi - lo + 1u;
@@ -215,7 +186,7 @@ __device__ __noinline__ bool sym_mem_ref(const DevSym S, const uint32_t *mem, si
             accw = pw;
         } else {
             uint32_t ct;
-            if (!sym_node_push(S, N, lane, SYM_CONCAT | ((accw + pw) << 8), acc, part, accw | (pw << 16), nn, ct))
+            if (!sym_node_push(S, N, lane, MG_SYM_CONCAT | ((accw + pw) << 8), acc, part, accw | (pw << 16), nn, ct))
                 return false;
             acc = ct - 1u;
             accw += pw;
@@ -243,15 +214,6 @@ DEV uint32_t sym_env_word(uint32_t op) {
     }
 }
 
-
-#define LANE_TAINT 2048u
-#define ESC_TAINT 9u
-#define TOBJ0 7u                  // MG_TAINT_OBJ0
-#define T_POST 16u
-#define T_EXPCOND 32u
-#define T_YCLASS 64u
-#define TREC_WORDS (MG_REC_HEADER + 11u)
-#define T_IFLANE (1u << 24)
 DEV uint32_t hrec_words(uint32_t n) { return MG_REC_HEADER + 8u * (n - 1u) + 3u; }
 
 DEV uint32_t t_obj(const DevTaint &T, size_t N, uint32_t lane, uint32_t slot) {
@@ -351,7 +313,8 @@ DEV void t_commit(const DevTaint &T, size_t N, uint32_t lane, uint32_t op, uint3
                   uint32_t sp0, uint32_t nsp, uint32_t nin, bool pushes, bool symcd, const U256 &a, const U256 &b,
                   bool b_sym, unsigned long long pre_bit, unsigned long long post_bit, uint32_t &nobj,
                   unsigned long long &sink, uint32_t &tf) {
-    const uint32_t pre_k = tact & 15u, sink_k = (tact >> 8) & 15u;
+    const uint32_t pre_k = MG_TAINT_FIELD(tact, MG_TAINT_PRE_SHIFT);
+    const uint32_t sink_k = MG_TAINT_FIELD(tact, MG_TAINT_SINK_SHIFT);
     if (pre_bit) {
         const uint32_t slot = sp0 - pre_k;
         uint32_t h = t_obj(T, N, lane, slot);
@@ -375,7 +338,7 @@ DEV void t_commit(const DevTaint &T, size_t N, uint32_t lane, uint32_t op, uint3
         uint32_t h = 0u;
         const uint32_t envw = sym_env_word(op);
         if (envw < 5u) h = envw + 1u;                     // environment.address/sender/... object
-        else if (op == 0x36u && symcd) h = 6u;            // SymbolicCalldata.calldatasize object
+        else if (op == 0x36u && symcd) h = MG_TAINT_CDSIZE;   // SymbolicCalldata.calldatasize object
         else {
             const unsigned long long rm = t_result_mask(T, N, lane, op, sp0, a, b, b_sym);
             if (rm) h = t_new(T, N, lane, nobj, rm);
@@ -400,14 +363,14 @@ __global__ __launch_bounds__(256) void k_sym_step(DevLanes L, DevSym S, DevTaint
     if ((threadIdx.x & 63u) < 2u) s_kc[(threadIdx.x >> 6) * KC_WAVE + KC_E * 24u + (threadIdx.x & 63u)] = 0u;
     __syncthreads();
     const uint32_t lane = blockIdx.x * blockDim.x + threadIdx.x;
-    if (lane >= L.n || L.status[lane] != ST_RUNNING) return;
+    if (lane >= L.n || L.status[lane] != MG_RUNNING) return;
     const uint32_t flags = L.flags[lane];
-    if (!(flags & (LANE_SYMBOLIC | LANE_TAINT))) return;
-    uint32_t lflags = flags;                 // + LANE_MEMTAG once a symbolic byte is written
+    if (!(flags & (MG_LANE_SYMBOLIC | MG_LANE_TAINT))) return;
+    uint32_t lflags = flags;                 // + MG_LANE_MEMTAG once a symbolic byte is written
     const size_t N = L.N;
     // symbolic semantics need the arena planes; taint needs the taint planes
-    const bool symlane = (flags & LANE_SYMBOLIC) && S.stag != nullptr;
-    const bool tl = (flags & LANE_TAINT) && T.sobj != nullptr;
+    const bool symlane = (flags & MG_LANE_SYMBOLIC) && S.stag != nullptr;
+    const bool tl = (flags & MG_LANE_TAINT) && T.sobj != nullptr;
     const DevCode C = codes[L.code_id[lane]];
     const uint8_t *__restrict__ gops = a8 + C.op_off;
     const uint8_t *__restrict__ gfent = a8 + C.fent_off;
@@ -415,7 +378,7 @@ __global__ __launch_bounds__(256) void k_sym_step(DevLanes L, DevSym S, DevTaint
     uint32_t fent = L.fent[lane];
     uint64_t gmin = L.gas_min[lane], gmax = L.gas_max[lane];
     const uint64_t txlim = L.gas_limit[lane];
-    const uint64_t glim = txlim < MSTATE_GAS_LIMIT + 1ull ? txlim : MSTATE_GAS_LIMIT + 1ull;
+    const uint64_t glim = txlim < MG_MSTATE_GAS_LIMIT + 1ull ? txlim : MG_MSTATE_GAS_LIMIT + 1ull;
     uint32_t nn = symlane ? S.n_nodes[lane] : 0u, nc = symlane ? S.n_consts[lane] : 0u;
     uint32_t nobj = 0u, tfixed = 0u, natoms = 0u, ttf = 0u;
     unsigned long long tsink = 0ull, tym = 0ull;
@@ -423,14 +386,14 @@ __global__ __launch_bounds__(256) void k_sym_step(DevLanes L, DevSym S, DevTaint
         nobj = T.n_obj[lane]; tfixed = T.n_fixed[lane]; natoms = T.n_atoms[lane]; ttf = T.tflags[lane];
         tsink = T.sink[lane]; tym = T.ymask[lane];
     }
-    const bool hook_ack = (flags & LANE_HOOK_ACK) != 0u;
-    const bool creation = (flags & LANE_CREATION) != 0u;
-    uint32_t lane_max = (flags & LANE_STEP1) ? min(max_steps, 1u) : max_steps;
+    const bool hook_ack = (flags & MG_LANE_HOOK_ACK) != 0u;
+    const bool creation = (flags & MG_LANE_CREATION) != 0u;
+    uint32_t lane_max = (flags & MG_LANE_STEP1) ? min(max_steps, 1u) : max_steps;
     if (horizon) {
         const uint32_t s0 = L.steps[lane];
         lane_max = min(lane_max, horizon > s0 ? horizon - s0 : 0u);
     }
-    uint32_t status = ST_RUNNING, aux = 0u, executed = 0u, n_sha3 = 0u, n_exp = 0u;
+    uint32_t status = MG_RUNNING, aux = 0u, executed = 0u, n_sha3 = 0u, n_exp = 0u;
     const bool loop_on = loop_bound != 0u && L.trace_cap != 0u;
     uint32_t tlen = loop_on ? L.trace_len[lane] : 0u;
     const LaneView V{L, lane, nullptr, 0u, threadIdx.x, 256u, nullptr, 0u};
@@ -444,8 +407,8 @@ __global__ __launch_bounds__(256) void k_sym_step(DevLanes L, DevSym S, DevTaint
     for (;;) {
         if (prof && executed != pexec) { atomicAdd(&prof[pop], 1ull); pexec = executed; }
         // the checks svm.execute_state makes before an instruction (svm.py:369-402)
-        if (max_depth != 0u && depth >= max_depth) { status = ST_DEPTH; break; }
-        if (pc >= C.n_instr) { status = ST_END; break; }
+        if (max_depth != 0u && depth >= max_depth) { status = MG_DEPTH; break; }
+        if (pc >= C.n_instr) { status = MG_HALT_END; break; }
         const uint32_t op = gops[pc];
         pop = op;
         const uint2 d = kDec[op];
@@ -459,22 +422,22 @@ __global__ __launch_bounds__(256) void k_sym_step(DevLanes L, DevSym S, DevTaint
                                            loop_bound, creation ? 1u : 0u);
             tlen = (uint32_t)tr;
             const uint32_t res = (uint32_t)(tr >> 60);
-            if (res == 1u) { status = ST_LOOP; aux = (uint32_t)(tr >> 32) & 0x0fffffffu; break; }
-            if (res == 2u) { status = ST_ESCAPE; aux = op | (ESC_TRACE << 8); break; }
+            if (res == 1u) { status = MG_LOOP_BOUND; aux = (uint32_t)(tr >> 32) & 0x0fffffffu; break; }
+            if (res == 2u) { status = MG_ESCAPE; aux = op | (MG_ESC_TRACE << 8); break; }
         }
-        if (hooked) { status = ST_HOOK; aux = op; break; }
+        if (hooked) { status = MG_HOOK; aux = op; break; }
         if (executed >= lane_max) break;
         const uint32_t uy = op | (d.y << 8) | pd_flags(op, d.y, 0u) | ((uint32_t)gfent[pc] << 22);
         // a creation's calldata opcodes run here on a lane with symbolic calldata (below)
         if (((uy & PD_SPECIAL) &&
-             !(((op == 0x47u && (flags & LANE_SYMBAL) && symlane) || (op == 0x31u && (flags & LANE_BALANCE) && symlane) ||
+             !(((op == 0x47u && (flags & MG_LANE_SYMBAL) && symlane) || (op == 0x31u && (flags & MG_LANE_BALANCE) && symlane) ||
                 ((op == 0x5au || op == 0x41u || op == 0x42u || op == 0x44u) && symlane) ||
-                ((op == 0x43u || op == 0x46u) && (flags & LANE_SYMBLOCK) && symlane)) && !tl)) ||
+                ((op == 0x43u || op == 0x46u) && (flags & MG_LANE_SYMBLOCK) && symlane)) && !tl)) ||
             // a creation's CODESIZE / CODECOPY / CALLDATA* run below only on a
             // symbolic-calldata lane without taint (the block that implements them
             // skips taint lanes); anywhere else the host steps them
-            (creation && (uy & PD_CREATION) && !(symlane && (flags & LANE_SYMCD) && !tl))) {
-            status = ST_ESCAPE; aux = op | (ESC_OPCODE << 8); break;
+            (creation && (uy & PD_CREATION) && !(symlane && (flags & MG_LANE_SYMCD) && !tl))) {
+            status = MG_ESCAPE; aux = op | (MG_ESC_OPCODE << 8); break;
         }
         const uint32_t req = d.y & 15u, npop = (d.y >> 4) & 15u;
         const bool pushes = ((d.y >> 8) & 1u) != 0u;
@@ -485,8 +448,8 @@ __global__ __launch_bounds__(256) void k_sym_step(DevLanes L, DevSym S, DevTaint
         if (symlane)
             for (uint32_t k = 0; k < nin && k < sp; ++k) any_sym |= sym_tag(S, N, lane, sp - 1u - k) != 0u;
         const uint32_t envw = sym_env_word(op);
-        const bool env_sym = symlane && envw < 5u && ((flags >> (LANE_SYMENV_SHIFT + envw)) & 1u);
-        const bool cd_sym = symlane && (flags & LANE_SYMCD) && (op == 0x35u || op == 0x36u || op == 0x37u);
+        const bool env_sym = symlane && envw < 5u && ((flags >> (MG_LANE_SYMENV_SHIFT + envw)) & 1u);
+        const bool cd_sym = symlane && (flags & MG_LANE_SYMCD) && (op == 0x35u || op == 0x36u || op == 0x37u);
         const bool stack_op = kind == K_DUP || kind == K_SWAP || kind == K_POP;
 
         // ---- taint lanes: this opcode's batch-safe hooks (mythril_amd/laser/taint.py) ----
@@ -499,15 +462,17 @@ __global__ __launch_bounds__(256) void k_sym_step(DevLanes L, DevSym S, DevTaint
         // of them (the host runs the hooks)
         if (tact && T.force) {
             const uint8_t f = T.force[C.cov_off + pc];
-            if (f == 1u) { status = ST_HOOK; aux = op; break; }
+            if (f == 1u) { status = MG_HOOK; aux = op; break; }
             if (f == 2u) tact = 0u;
         }
         if (tact) {
-            const uint32_t yk = (tact >> 12) & 15u, pre_k = tact & 15u;
-            const uint32_t dk = (tact >> 16) & 15u, sk = (tact >> 20) & 15u;
+            const uint32_t pre_k = MG_TAINT_FIELD(tact, MG_TAINT_PRE_SHIFT);
+            const uint32_t yk = MG_TAINT_FIELD(tact, MG_TAINT_YIELD_SHIFT);
+            const uint32_t dk = MG_TAINT_FIELD(tact, MG_TAINT_DEFER_SHIFT);
+            const uint32_t sk = MG_TAINT_FIELD(tact, MG_TAINT_IFSYM_SHIFT);
             // a yield-if hook has work only when its operand carries an atom of the class
             if (yk && sp >= yk && (t_mask(T, N, lane, t_obj(T, N, lane, sp - yk)) & tym)) {
-                status = ST_HOOK; aux = op; break;
+                status = MG_HOOK; aux = op; break;
             }
             // hooks with work only on a symbolic operand, or on lanes whose state
             // carries a given annotation; a deferred hook's words must be concrete
@@ -516,16 +481,16 @@ __global__ __launch_bounds__(256) void k_sym_step(DevLanes L, DevSym S, DevTaint
                 if (sk && sp >= sk && sym_tag(S, N, lane, sp - sk)) ysym = true;
                 for (uint32_t j = 0; j < dk && j < sp; ++j) ysym |= sym_tag(S, N, lane, sp - 1u - j) != 0u;
             }
-            if (ysym || ((tact & T_IFLANE) && (ttf & 2u))) { status = ST_HOOK; aux = op; break; }
+            if (ysym || ((tact & MG_TAINT_IFLANE) && (ttf & 2u))) { status = MG_HOOK; aux = op; break; }
             bool do_pre = pre_k != 0u && sp >= pre_k && sp >= req;
-            const bool do_post = (tact & T_POST) != 0u;
+            const bool do_post = (tact & MG_TAINT_POST) != 0u;
             if (do_pre || do_post) {
                 // the device replays annotating hooks on concrete words only; the host
                 // runs them (MG_HOOK) on symbolic ones and around SHA3/EXP results
                 if (any_sym || env_sym || cd_sym || (do_post && (kind == K_SHA3 || op == 0x0au))) {
-                    status = ST_HOOK; aux = op; break;
+                    status = MG_HOOK; aux = op; break;
                 }
-                if (do_pre && (tact & T_EXPCOND)) {
+                if (do_pre && (tact & MG_TAINT_EXPCOND)) {
                     // integer.py:161-166: no annotation for exponent 0 or base < 2
                     const U256 base = V.stack(sp - 1u);
                     const U256 ex = sp >= 2u ? V.stack(sp - 2u) : u_zero();
@@ -534,21 +499,21 @@ __global__ __launch_bounds__(256) void k_sym_step(DevLanes L, DevSym S, DevTaint
             }
             const uint32_t need = (do_pre ? 1u : 0u) + (do_post ? 1u : 0u);
             const bool defer = dk != 0u && sp >= dk;
-            if (natoms + need > 64u) { status = ST_ESCAPE; aux = op | (ESC_TAINT << 8); break; }
+            if (natoms + need > MG_TAINT_MAX_ATOMS) { status = MG_ESCAPE; aux = op | (MG_ESC_TAINT << 8); break; }
             if (nobj + 4u > T.obj_cap) {
                 t_gc(T, N, lane, sp, tfixed, nobj);
-                if (nobj + 4u > T.obj_cap) { status = ST_ESCAPE; aux = op | (ESC_TAINT << 8); break; }
+                if (nobj + 4u > T.obj_cap) { status = MG_ESCAPE; aux = op | (MG_ESC_TAINT << 8); break; }
             }
-            if ((need || defer) && (uint64_t)L.rec_len[lane] + need * TREC_WORDS + (defer ? hrec_words(dk) : 0u) >
+            if ((need || defer) && (uint64_t)L.rec_len[lane] + need * MG_REC_ANNOT_WORDS + (defer ? hrec_words(dk) : 0u) >
                                        L.rec_cap) {
-                status = ST_ESCAPE; aux = op | (ESC_RECORD << 8); break;
+                status = MG_ESCAPE; aux = op | (MG_ESC_RECORD << 8); break;
             }
             rec_save = L.rec_len[lane];
             if (do_pre) {
                 // logged before the mutator runs: its own records (EXP) follow
                 rec_annot(L, lane, L.rec_len[lane], natoms, L.steps[lane] + executed, V.stack(sp - 1u),
                           sp >= 2u ? V.stack(sp - 2u) : u_zero(), pc, op, fent);
-                L.rec_len[lane] += TREC_WORDS;
+                L.rec_len[lane] += MG_REC_ANNOT_WORDS;
                 rec_pre = true;
                 pre_bit = 1ull << natoms;
             }
@@ -562,7 +527,7 @@ __global__ __launch_bounds__(256) void k_sym_step(DevLanes L, DevSym S, DevTaint
             if (do_post) post_bit = 1ull << (natoms + (do_pre ? 1u : 0u));
         } else if (tl && nobj + 4u > T.obj_cap) {
             t_gc(T, N, lane, sp, tfixed, nobj);
-            if (nobj + 4u > T.obj_cap) { status = ST_ESCAPE; aux = op | (ESC_TAINT << 8); break; }
+            if (nobj + 4u > T.obj_cap) { status = MG_ESCAPE; aux = op | (MG_ESC_TAINT << 8); break; }
         }
 
         // ---- symbolic calldata into memory, and a creation's calldata opcodes ----
@@ -577,32 +542,32 @@ __global__ __launch_bounds__(256) void k_sym_step(DevLanes L, DevSym S, DevTaint
         // the code's size.  A message call's CALLDATACOPY with a symbolic memory offset
         // copies nothing and one with a symbolic size copies 320 bytes, as the
         // reference does; a symbolic calldata offset stays with the host.
-        if (symlane && (flags & LANE_SYMCD) && !tl && sp >= max(req, npop) &&
+        if (symlane && (flags & MG_LANE_SYMCD) && !tl && sp >= max(req, npop) &&
             (op == 0x37u || (creation && op == 0x38u) ||
              (creation && op == 0x39u && !sym_tag(S, N, lane, sp - 2u) &&
               !(u_fits32(V.stack(sp - 2u)) && V.stack(sp - 2u).w[0] < C.n_bytes)))) {
             const uint64_t gtmin = d.x & 0xffffu, gtmax = d.x >> 16;
-            uint32_t nsp = sp - npop, nmsize = msize, lnn = nn, stop = ST_RUNNING, sx = 0u, rec_new = 0u;
+            uint32_t nsp = sp - npop, nmsize = msize, lnn = nn, stop = MG_RUNNING, sx = 0u, rec_new = 0u;
             uint64_t ngmin = gmin, ngmax = gmax;
             U256 rval = u_zero();
             bool wrote_tag = false;
             do {
 #define CSTOPX(s_, x_) { stop = (s_); sx = (x_); break; }
                 if (op == 0x38u) {                                   // creation CODESIZE
-                    if (nsp + 1u > STACK_LIMIT) CSTOPX(ST_VMEXC, EXC_OVERFLOW)
-                    if (nsp + 1u > L.stack_cap) CSTOPX(ST_ESCAPE, op | (ESC_STACK << 8))
+                    if (nsp + 1u > MG_STACK_LIMIT) CSTOPX(MG_VMEXC, MG_EXC_STACK_OVERFLOW)
+                    if (nsp + 1u > L.stack_cap) CSTOPX(MG_ESCAPE, op | (MG_ESC_STACK << 8))
                     const uint32_t rec_at = L.rec_len[lane];
                     if (!L.rec_cap || (uint64_t)rec_at + MG_REC_HEADER > L.rec_cap)
-                        CSTOPX(ST_ESCAPE, op | (ESC_RECORD << 8))
+                        CSTOPX(MG_ESCAPE, op | (MG_ESC_RECORD << 8))
                     ngmin += gtmin; ngmax += gtmax;
-                    if (ngmin >= glim) CSTOPX(ST_VMEXC, EXC_OOG)
+                    if (ngmin >= glim) CSTOPX(MG_VMEXC, MG_EXC_OUT_OF_GAS)
                     rval = u_small(C.n_bytes + 0x200u);
                     rec_new = rec_head(L, lane, rec_at, MG_REC_CDSIZE, 0u, L.steps[lane] + executed, rval);
                     break;
                 }
                 if (creation && op == 0x37u) {                       // creation CALLDATACOPY: pops only
                     ngmin += gtmin; ngmax += gtmax;
-                    if (ngmin >= glim) CSTOPX(ST_VMEXC, EXC_OOG)
+                    if (ngmin >= glim) CSTOPX(MG_VMEXC, MG_EXC_OUT_OF_GAS)
                     break;
                 }
                 const uint32_t ta = sym_tag(S, N, lane, sp - 1u), tb = sym_tag(S, N, lane, sp - 2u);
@@ -611,47 +576,47 @@ __global__ __launch_bounds__(256) void k_sym_step(DevLanes L, DevSym S, DevTaint
                 if (op == 0x37u && ta) {
                     // a symbolic memory offset: the copy is dropped (instructions.py:810-814)
                     ngmin += gtmin; ngmax += gtmax;
-                    if (ngmin >= glim) CSTOPX(ST_VMEXC, EXC_OOG)
+                    if (ngmin >= glim) CSTOPX(MG_VMEXC, MG_EXC_OUT_OF_GAS)
                     break;
                 }
                 // a symbolic size copies SYMBOLIC_CALLDATA_SIZE bytes (instructions.py:822-826,
                 // call.py:33); a symbolic calldata offset y makes byte k calldata[y + k]
                 const bool symsrc = op == 0x37u && tb != 0u;
                 if (op == 0x37u && tc) { c = u_small(320u); tc = 0u; }
-                if (ta || (tb && !symsrc) || tc) CSTOPX(ST_ESCAPE, op | (ESC_SYMBOLIC << 8))
+                if (ta || (tb && !symsrc) || tc) CSTOPX(MG_ESCAPE, op | (MG_ESC_SYMBOLIC << 8))
                 if (u_iszero(c)) {                                   // size 0: nothing but the gas
                     ngmin += gtmin; ngmax += gtmax;
-                    if (ngmin >= glim) CSTOPX(ST_VMEXC, EXC_OOG)
+                    if (ngmin >= glim) CSTOPX(MG_VMEXC, MG_EXC_OUT_OF_GAS)
                     break;
                 }
                 const int mx = mem_extend(a, c, nmsize, ngmin, ngmax, L.mem_cap, (int64_t)gtmin, txlim);
-                if (mx == MX_OOG) CSTOPX(ST_VMEXC, EXC_OOG)
-                if (mx == MX_ESCAPE) CSTOPX(ST_ESCAPE, op | (ESC_MEMORY << 8))
+                if (mx == MX_OOG) CSTOPX(MG_VMEXC, MG_EXC_OUT_OF_GAS)
+                if (mx == MX_ESCAPE) CSTOPX(MG_ESCAPE, op | (MG_ESC_MEMORY << 8))
                 ngmin += gtmin; ngmax += gtmax;
-                if (ngmin >= glim) CSTOPX(ST_VMEXC, EXC_OOG)
+                if (ngmin >= glim) CSTOPX(MG_VMEXC, MG_EXC_OUT_OF_GAS)
                 // the source index of every byte must stay below 2^32 on the device
                 const uint32_t src = op == 0x39u ? b.w[0] - C.n_bytes : b.w[0];
                 const uint32_t size = c.w[0], mst = a.w[0];
                 if (!symsrc && (!u_fits32(b) || (uint64_t)src + size > 0xffffffffull))
-                    CSTOPX(ST_ESCAPE, op | (ESC_SYMBOLIC << 8))
-                if ((uint64_t)lnn + size > S.node_cap) CSTOPX(ST_ESCAPE, op | (ESC_ARENA << 8))
+                    CSTOPX(MG_ESCAPE, op | (MG_ESC_SYMBOLIC << 8))
+                if ((uint64_t)lnn + size > S.node_cap) CSTOPX(MG_ESCAPE, op | (MG_ESC_ARENA << 8))
                 if (nmsize > msize) V.mzero(msize, nmsize);
                 for (uint32_t k = 0; k < size; ++k) {
                     uint32_t tg;
-                    if (symsrc) sym_node_push(S, N, lane, SYM_CDBYTEX | (8u << 8), tb - 1u, 0u, k, lnn, tg);
-                    else sym_node_push(S, N, lane, SYM_CDBYTE | (8u << 8), 0u, 0u, src + k, lnn, tg);
+                    if (symsrc) sym_node_push(S, N, lane, MG_SYM_CDBYTEX | (8u << 8), tb - 1u, 0u, k, lnn, tg);
+                    else sym_node_push(S, N, lane, MG_SYM_CDBYTE | (8u << 8), 0u, 0u, src + k, lnn, tg);
                     V.set_mbyte(mst + k, 0u);
                     set_mtag(S, N, lane, mst + k, 1u + (((tg - 1u) << 5) | 31u));
                 }
                 wrote_tag = true;
 #undef CSTOPX
             } while (0);
-            if (stop != ST_RUNNING) {
-                if (stop != ST_ESCAPE) ++executed;
+            if (stop != MG_RUNNING) {
+                if (stop != MG_ESCAPE) ++executed;
                 status = stop; aux = sx; break;
             }
             if (rec_new) L.rec_len[lane] = rec_new;
-            if (wrote_tag) lflags |= LANE_MEMTAG;
+            if (wrote_tag) lflags |= MG_LANE_MEMTAG;
             if (op == 0x38u) {
                 V.set_stack(nsp, rval);
                 sym_set_tag(S, N, lane, nsp, 0u);
@@ -676,11 +641,11 @@ __global__ __launch_bounds__(256) void k_sym_step(DevLanes L, DevSym S, DevTaint
             const uint32_t tb0 = npop >= 2u ? sym_tag(S, N, lane, sp - 2u) : 0u;
             if (kind == K_SLOAD || kind == K_SSTORE) memlane = true;
             else if (kind == K_MLOAD || kind == K_MSTORE || kind == K_MSTORE8)
-                memlane = ta0 != 0u || tb0 != 0u || (lflags & LANE_MEMTAG);
+                memlane = ta0 != 0u || tb0 != 0u || (lflags & MG_LANE_MEMTAG);
             else if (kind == K_SHA3) {
                 const U256 a0 = V.stack(sp - 1u), b0 = V.stack(sp - 2u);
                 memlane = ta0 != 0u || tb0 != 0u ||
-                          ((lflags & LANE_MEMTAG) && u_fits32(a0) && u_fits32(b0) && b0.w[0] != 0u &&
+                          ((lflags & MG_LANE_MEMTAG) && u_fits32(a0) && u_fits32(b0) && b0.w[0] != 0u &&
                            mtag_any(S, N, lane, a0.w[0], b0.w[0], msize));
             }
         }
@@ -690,7 +655,7 @@ __global__ __launch_bounds__(256) void k_sym_step(DevLanes L, DevSym S, DevTaint
             const U256 a = V.stack(sp - 1u);
             const U256 b = npop >= 2u ? V.stack(sp - 2u) : u_zero();
             const uint32_t nsp = sp - npop;
-            uint32_t lnn = nn, lnc = nc, rtag = 0u, nmsize = msize, rec_new = 0u, stop = ST_RUNNING, sx = 0u;
+            uint32_t lnn = nn, lnc = nc, rtag = 0u, nmsize = msize, rec_new = 0u, stop = MG_RUNNING, sx = 0u;
             uint64_t ngmin = gmin, ngmax = gmax;
             U256 rval = u_zero();
             bool wrote_tag = false;
@@ -700,15 +665,15 @@ __global__ __launch_bounds__(256) void k_sym_step(DevLanes L, DevSym S, DevTaint
             const bool tbusy = tl && (pre_bit != 0ull || post_bit != 0ull);
             const bool memsym = kind != K_SLOAD && kind != K_SSTORE;
             do {
-                if (tbusy) { stop = ST_HOOK; sx = op; break; }
+                if (tbusy) { stop = MG_HOOK; sx = op; break; }
 #define MSTOPX(s_, x_) { stop = (s_); sx = (x_); break; }
-#define MGAS() { ngmin += gtmin; ngmax += gtmax; if (ngmin >= glim) MSTOPX(ST_VMEXC, EXC_OOG) }
-#define MPUSHCHK() { if (nsp + 1u > STACK_LIMIT) MSTOPX(ST_VMEXC, EXC_OVERFLOW) \
-                     if (nsp + 1u > L.stack_cap) MSTOPX(ST_ESCAPE, op | (ESC_STACK << 8)) }
+#define MGAS() { ngmin += gtmin; ngmax += gtmax; if (ngmin >= glim) MSTOPX(MG_VMEXC, MG_EXC_OUT_OF_GAS) }
+#define MPUSHCHK() { if (nsp + 1u > MG_STACK_LIMIT) MSTOPX(MG_VMEXC, MG_EXC_STACK_OVERFLOW) \
+                     if (nsp + 1u > L.stack_cap) MSTOPX(MG_ESCAPE, op | (MG_ESC_STACK << 8)) }
 #define MMEMX(st_, sz_, later_) { const int mx_ = mem_extend((st_), (sz_), nmsize, ngmin, ngmax, L.mem_cap, \
                                                              (later_), txlim); \
-                                  if (mx_ == MX_OOG) MSTOPX(ST_VMEXC, EXC_OOG) \
-                                  if (mx_ == MX_ESCAPE) MSTOPX(ST_ESCAPE, op | (ESC_MEMORY << 8)) }
+                                  if (mx_ == MX_OOG) MSTOPX(MG_VMEXC, MG_EXC_OUT_OF_GAS) \
+                                  if (mx_ == MX_ESCAPE) MSTOPX(MG_ESCAPE, op | (MG_ESC_MEMORY << 8)) }
                 if (memsym && ta) {
                     // a symbolic offset: the reference keys its byte map by simplify(index)
                     // (memory.py:117-203).  MSTORE / MSTORE8 append an event node (offset,
@@ -719,23 +684,23 @@ __global__ __launch_bounds__(256) void k_sym_step(DevLanes L, DevSym S, DevTaint
                     // SHA3 of a concrete length reads the same way: an MLOADK node over
                     // [offset, offset + length) feeds a KECCAK node (sha3_, instructions.py:
                     // 1014-1051).  A symbolic or zero length and taint lanes stay with the host.
-                    if (tl) MSTOPX(ST_ESCAPE, op | (ESC_SYMBOLIC << 8))
+                    if (tl) MSTOPX(MG_ESCAPE, op | (MG_ESC_SYMBOLIC << 8))
                     if (kind == K_SHA3) {
                         if (tb || !u_fits32(b) || b.w[0] == 0u || b.w[0] > 4096u)
-                            MSTOPX(ST_ESCAPE, op | (ESC_SYMBOLIC << 8))
+                            MSTOPX(MG_ESCAPE, op | (MG_ESC_SYMBOLIC << 8))
                         const uint32_t len = b.w[0];
-                        if (!L.rec_cap) MSTOPX(ST_ESCAPE, op | (ESC_SYMBOLIC << 8))
+                        if (!L.rec_cap) MSTOPX(MG_ESCAPE, op | (MG_ESC_SYMBOLIC << 8))
                         const uint64_t g = 30ull + 6ull * (((uint64_t)len + 31ull) >> 5);
                         ngmin += g; ngmax += g;
-                        if (ngmin >= glim) MSTOPX(ST_VMEXC, EXC_OOG)
+                        if (ngmin >= glim) MSTOPX(MG_VMEXC, MG_EXC_OUT_OF_GAS)
                         const uint32_t rec_at = L.rec_len[lane];
                         if ((uint64_t)rec_at + MG_REC_HEADER + 1u > L.rec_cap)
-                            MSTOPX(ST_ESCAPE, op | (ESC_RECORD << 8))
+                            MSTOPX(MG_ESCAPE, op | (MG_ESC_RECORD << 8))
                         MPUSHCHK()
                         uint32_t mt;
-                        if (!sym_node_push(S, N, lane, SYM_MLOADK | ((8u * len) << 8), ta - 1u, 0u, len, lnn, mt) ||
-                            !sym_node_push(S, N, lane, SYM_KECCAK | (256u << 8), mt - 1u, 0u, 8u * len, lnn, rtag))
-                            MSTOPX(ST_ESCAPE, op | (ESC_ARENA << 8))
+                        if (!sym_node_push(S, N, lane, MG_SYM_MLOADK | ((8u * len) << 8), ta - 1u, 0u, len, lnn, mt) ||
+                            !sym_node_push(S, N, lane, MG_SYM_KECCAK | (256u << 8), mt - 1u, 0u, 8u * len, lnn, rtag))
+                            MSTOPX(MG_ESCAPE, op | (MG_ESC_ARENA << 8))
                         rec_new = rec_head(L, lane, rec_at, MG_REC_SYMKECCAK, len, L.steps[lane] + executed, u_zero());
                         L.rec[(size_t)rec_new * N + lane] = rtag - 1u;
                         ++rec_new;
@@ -743,15 +708,15 @@ __global__ __launch_bounds__(256) void k_sym_step(DevLanes L, DevSym S, DevTaint
                     } else if (kind == K_MLOAD) {
                         MPUSHCHK()
                         MGAS()
-                        if (!sym_node_push(S, N, lane, SYM_MLOADK | (256u << 8), ta - 1u, 0u, 0u, lnn, rtag))
-                            MSTOPX(ST_ESCAPE, op | (ESC_ARENA << 8))
+                        if (!sym_node_push(S, N, lane, MG_SYM_MLOADK | (256u << 8), ta - 1u, 0u, 0u, lnn, rtag))
+                            MSTOPX(MG_ESCAPE, op | (MG_ESC_ARENA << 8))
                     } else {
                         MGAS()
                         uint32_t vref, et;
                         if (!sym_ref(S, N, lane, tb, b, lnc, vref) ||
-                            !sym_node_push(S, N, lane, SYM_MSTOREK, ta - 1u, vref, kind == K_MSTORE8 ? 2u : 1u,
+                            !sym_node_push(S, N, lane, MG_SYM_MSTOREK, ta - 1u, vref, kind == K_MSTORE8 ? 2u : 1u,
                                            lnn, et))
-                            MSTOPX(ST_ESCAPE, op | (ESC_ARENA << 8))
+                            MSTOPX(MG_ESCAPE, op | (MG_ESC_ARENA << 8))
                     }
                     break;
                 }
@@ -777,19 +742,19 @@ __global__ __launch_bounds__(256) void k_sym_step(DevLanes L, DevSym S, DevTaint
                         const uint2 tg = S.sttag[(size_t)e * N + lane];
                         if (tg.y) rtag = tg.y;
                         else rval = ld_word(gv(L.storage), V.row((uint32_t)e) * 2 + 1);
-                    } else if (e < 0 && !(lflags & LANE_SYMSTORE)) {
+                    } else if (e < 0 && !(lflags & MG_LANE_SYMSTORE)) {
                         rval = u_zero();                             // K(256, 256, 0): its default
                     } else {
                         uint32_t ya;
                         if (!sym_ref(S, N, lane, ta, a, lnc, ya) ||
-                            !sym_node_push(S, N, lane, SYM_SLOAD | (256u << 8), ya, cnt, 0u, lnn, rtag))
-                            MSTOPX(ST_ESCAPE, op | (ESC_ARENA << 8))
+                            !sym_node_push(S, N, lane, MG_SYM_SLOAD | (256u << 8), ya, cnt, 0u, lnn, rtag))
+                            MSTOPX(MG_ESCAPE, op | (MG_ESC_ARENA << 8))
                     }
                 } else if (kind == K_SSTORE) {
                     // a new Store on the chain (account.py:77-87), never in place
-                    if (flags & LANE_STATIC) MSTOPX(ST_VMEXC, EXC_WRITEPROT)
+                    if (flags & MG_LANE_STATIC) MSTOPX(MG_VMEXC, MG_EXC_WRITE_PROTECTION)
                     const uint32_t cnt = L.storage_count[lane];
-                    if (cnt >= L.storage_cap) MSTOPX(ST_ESCAPE, op | (ESC_STORAGE << 8))
+                    if (cnt >= L.storage_cap) MSTOPX(MG_ESCAPE, op | (MG_ESC_STORAGE << 8))
                     MGAS()
                     st_word(gv(L.storage), V.row(cnt) * 2, ta ? u_zero() : a);
                     st_word(gv(L.storage), V.row(cnt) * 2 + 1, tb ? u_zero() : b);
@@ -800,18 +765,18 @@ __global__ __launch_bounds__(256) void k_sym_step(DevLanes L, DevSym S, DevTaint
                     MPUSHCHK()
                     MGAS()
                     if (nmsize > msize) V.mzero(msize, nmsize);
-                    if ((lflags & LANE_MEMTAG) && mtag_any(S, N, lane, a.w[0], 32u, nmsize)) {
-                        if (tl) MSTOPX(ST_ESCAPE, op | (ESC_SYMBOLIC << 8))
+                    if ((lflags & MG_LANE_MEMTAG) && mtag_any(S, N, lane, a.w[0], 32u, nmsize)) {
+                        if (tl) MSTOPX(MG_ESCAPE, op | (MG_ESC_SYMBOLIC << 8))
                         uint32_t r;
                         if (!sym_mem_ref(S, L.mem, N, lane, a.w[0], 32u, nmsize, lnn, lnc, r))
-                            MSTOPX(ST_ESCAPE, op | (ESC_ARENA << 8))
+                            MSTOPX(MG_ESCAPE, op | (MG_ESC_ARENA << 8))
                         rtag = r + 1u;
                     } else {
                         rval = V.mword(a.w[0]);
                     }
                 } else if (kind == K_MSTORE || kind == K_MSTORE8) {
                     const bool m8 = kind == K_MSTORE8;
-                    if (tb && tl) MSTOPX(ST_ESCAPE, op | (ESC_SYMBOLIC << 8))
+                    if (tb && tl) MSTOPX(MG_ESCAPE, op | (MG_ESC_SYMBOLIC << 8))
                     MMEMX(a, u_small(m8 ? 1u : 32u), (int64_t)gtmin)
                     MGAS()
                     if (nmsize > msize) V.mzero(msize, nmsize);
@@ -831,29 +796,29 @@ __global__ __launch_bounds__(256) void k_sym_step(DevLanes L, DevSym S, DevTaint
                     } else {
                         if (m8) V.set_mbyte(off, b.w[0] & 0xffu);
                         else V.set_mword(off, b);
-                        if (lflags & LANE_MEMTAG)
+                        if (lflags & MG_LANE_MEMTAG)
                             for (uint32_t j = 0; j < (m8 ? 1u : 32u); ++j) set_mtag(S, N, lane, off + j, 0u);
                     }
                 } else {  // K_SHA3 over symbolic bytes: keccak256_<8 len>(data), create_keccak
-                    if (tl) MSTOPX(ST_ESCAPE, op | (ESC_SYMBOLIC << 8))
+                    if (tl) MSTOPX(MG_ESCAPE, op | (MG_ESC_SYMBOLIC << 8))
                     // a symbolic length is taken as 64 with `length == 64` appended to the
                     // path (instructions.py:1023-1028, an MG_REC_SYMLEN record before the
                     // SHA3's own); only over a range holding a symbolic byte, so the data
                     // (and the hash) stay symbolic as in the reference
                     if (tb && (sym_width(S, N, lane, tb) == 1u || !u_fits32(a) ||
-                               !((lflags & LANE_MEMTAG) && mtag_any(S, N, lane, a.w[0], 64u, msize))))
-                        MSTOPX(ST_ESCAPE, op | (ESC_SYMBOLIC << 8))
+                               !((lflags & MG_LANE_MEMTAG) && mtag_any(S, N, lane, a.w[0], 64u, msize))))
+                        MSTOPX(MG_ESCAPE, op | (MG_ESC_SYMBOLIC << 8))
                     const uint32_t len = tb ? 64u : b.w[0];
-                    if (!L.rec_cap) MSTOPX(ST_ESCAPE, op | (ESC_SYMBOLIC << 8))
+                    if (!L.rec_cap) MSTOPX(MG_ESCAPE, op | (MG_ESC_SYMBOLIC << 8))
                     const uint64_t g = 30ull + 6ull * (((uint64_t)len + 31ull) >> 5);
                     ngmin += g; ngmax += g;
                     // the reference has appended the length constraint before this check:
                     // an out-of-gas SHA3 of a symbolic length is the host's
-                    if (ngmin >= glim) MSTOPX(tb ? ST_ESCAPE : ST_VMEXC, tb ? op | (ESC_SYMBOLIC << 8) : EXC_OOG)
+                    if (ngmin >= glim) MSTOPX(tb ? MG_ESCAPE : MG_VMEXC, tb ? op | (MG_ESC_SYMBOLIC << 8) : MG_EXC_OUT_OF_GAS)
                     MMEMX(a, u_small(len), -1)
                     uint32_t rec_at = L.rec_len[lane];
                     const uint32_t rec_need = (tb ? MG_REC_HEADER + 1u : 0u) + MG_REC_HEADER + 1u;
-                    if ((uint64_t)rec_at + rec_need > L.rec_cap) MSTOPX(ST_ESCAPE, op | (ESC_RECORD << 8))
+                    if ((uint64_t)rec_at + rec_need > L.rec_cap) MSTOPX(MG_ESCAPE, op | (MG_ESC_RECORD << 8))
                     if (tb) {
                         const uint32_t at = rec_head(L, lane, rec_at, MG_REC_SYMLEN, 64u, L.steps[lane] + executed,
                                                      u_zero());
@@ -864,8 +829,8 @@ __global__ __launch_bounds__(256) void k_sym_step(DevLanes L, DevSym S, DevTaint
                     MPUSHCHK()
                     uint32_t r;
                     if (!sym_mem_ref(S, L.mem, N, lane, a.w[0], len, nmsize, lnn, lnc, r) ||
-                        !sym_node_push(S, N, lane, SYM_KECCAK | (256u << 8), r, 0u, 8u * len, lnn, rtag))
-                        MSTOPX(ST_ESCAPE, op | (ESC_ARENA << 8))
+                        !sym_node_push(S, N, lane, MG_SYM_KECCAK | (256u << 8), r, 0u, 8u * len, lnn, rtag))
+                        MSTOPX(MG_ESCAPE, op | (MG_ESC_ARENA << 8))
                     rec_new = rec_head(L, lane, rec_at, MG_REC_SYMKECCAK, len, L.steps[lane] + executed, u_zero());
                     L.rec[(size_t)rec_new * N + lane] = rtag - 1u;
                     ++rec_new;
@@ -876,13 +841,13 @@ __global__ __launch_bounds__(256) void k_sym_step(DevLanes L, DevSym S, DevTaint
 #undef MPUSHCHK
 #undef MMEMX
             } while (0);
-            if (stop != ST_RUNNING) {
+            if (stop != MG_RUNNING) {
                 if (rec_pre) L.rec_len[lane] = rec_save;   // the instruction did not run
-                if (stop != ST_ESCAPE && stop != ST_HOOK) ++executed;
+                if (stop != MG_ESCAPE && stop != MG_HOOK) ++executed;
                 status = stop; aux = sx; break;
             }
             if (rec_new) L.rec_len[lane] = rec_new;
-            if (wrote_tag) lflags |= LANE_MEMTAG;
+            if (wrote_tag) lflags |= MG_LANE_MEMTAG;
             if (tl)
                 t_commit(T, N, lane, op, kind, tact, sp, nsp + (pushes ? 1u : 0u), nin, pushes, false, a, b, tb != 0u,
                          pre_bit, post_bit, nobj, tsink, ttf);
@@ -891,13 +856,13 @@ __global__ __launch_bounds__(256) void k_sym_step(DevLanes L, DevSym S, DevTaint
                 sym_set_tag(S, N, lane, nsp, rtag);
             }
             sp = nsp + (pushes ? 1u : 0u); ++pc; msize = nmsize; gmin = ngmin; gmax = ngmax; nn = lnn; nc = lnc;
-            if (pre_bit) { ++natoms; if (tact & T_YCLASS) tym |= pre_bit; }
+            if (pre_bit) { ++natoms; if (tact & MG_TAINT_YCLASS) tym |= pre_bit; }
             ++executed;
             continue;
         }
 
         if (op == 0x47u || op == 0x5au || op == 0x41u || op == 0x42u || op == 0x44u || op == 0x43u || op == 0x46u ||
-            (op == 0x3du && (flags & LANE_SYMRDS) && !tl)) {
+            (op == 0x3du && (flags & MG_LANE_SYMRDS) && !tl)) {
             // SELFBALANCE on a lane whose balance is symbolic (selfbalance_,
             // instructions.py:968-976; taint lanes escaped above):
             // environment.active_account.balance(), the balances array at the active
@@ -915,12 +880,12 @@ __global__ __launch_bounds__(256) void k_sym_step(DevLanes L, DevSym S, DevTaint
                                    op == 0x46u ? MG_ENV_CHAINID : MG_ENV_RETURNDATASIZE;
             const uint64_t ngmin = gmin + (d.x & 0xffffu), ngmax = gmax + (d.x >> 16);
             uint32_t lnn = nn, rtag = 0u;
-            if (sp + 1u > STACK_LIMIT) { ++executed; status = ST_VMEXC; aux = EXC_OVERFLOW; break; }
-            if (sp + 1u > L.stack_cap) { status = ST_ESCAPE; aux = op | (ESC_STACK << 8); break; }
-            if (!sym_node_push(S, N, lane, SYM_ENV | (256u << 8), 0u, 0u, which, lnn, rtag)) {
-                status = ST_ESCAPE; aux = op | (ESC_ARENA << 8); break;
+            if (sp + 1u > MG_STACK_LIMIT) { ++executed; status = MG_VMEXC; aux = MG_EXC_STACK_OVERFLOW; break; }
+            if (sp + 1u > L.stack_cap) { status = MG_ESCAPE; aux = op | (MG_ESC_STACK << 8); break; }
+            if (!sym_node_push(S, N, lane, MG_SYM_ENV | (256u << 8), 0u, 0u, which, lnn, rtag)) {
+                status = MG_ESCAPE; aux = op | (MG_ESC_ARENA << 8); break;
             }
-            if (ngmin >= glim) { ++executed; status = ST_VMEXC; aux = EXC_OOG; break; }
+            if (ngmin >= glim) { ++executed; status = MG_VMEXC; aux = MG_EXC_OUT_OF_GAS; break; }
             V.set_stack(sp, u_zero());
             sym_set_tag(S, N, lane, sp, rtag);
             ++sp; ++pc; gmin = ngmin; gmax = ngmax; nn = lnn;
@@ -934,17 +899,17 @@ __global__ __launch_bounds__(256) void k_sym_step(DevLanes L, DevSym S, DevTaint
             // account.address, account.balance(), ...) over the world state's accounts.
             // A BALANCE node over the address; the host builds the term from the lane's
             // world state, which no device instruction changes.
-            if (sp < 1u) { status = ST_ESCAPE; aux = op | (ESC_SYMBOLIC << 8); break; }   // the host's underflow
+            if (sp < 1u) { status = MG_ESCAPE; aux = op | (MG_ESC_SYMBOLIC << 8); break; }   // the host's underflow
             const U256 a = V.stack(sp - 1u);
             const uint32_t ta = sym_tag(S, N, lane, sp - 1u);
-            if (ta && sym_width(S, N, lane, ta) == 1u) { status = ST_ESCAPE; aux = op | (ESC_SYMBOLIC << 8); break; }
+            if (ta && sym_width(S, N, lane, ta) == 1u) { status = MG_ESCAPE; aux = op | (MG_ESC_SYMBOLIC << 8); break; }
             const uint64_t ngmin = gmin + (d.x & 0xffffu), ngmax = gmax + (d.x >> 16);
             uint32_t lnn = nn, lnc = nc, ya = 0u, rtag = 0u;
             if (!sym_ref(S, N, lane, ta, a, lnc, ya) ||
-                !sym_node_push(S, N, lane, SYM_BALANCE | (256u << 8), ya, 0u, 0u, lnn, rtag)) {
-                status = ST_ESCAPE; aux = op | (ESC_ARENA << 8); break;
+                !sym_node_push(S, N, lane, MG_SYM_BALANCE | (256u << 8), ya, 0u, 0u, lnn, rtag)) {
+                status = MG_ESCAPE; aux = op | (MG_ESC_ARENA << 8); break;
             }
-            if (ngmin >= glim) { ++executed; status = ST_VMEXC; aux = EXC_OOG; break; }
+            if (ngmin >= glim) { ++executed; status = MG_VMEXC; aux = MG_EXC_OUT_OF_GAS; break; }
             V.set_stack(sp - 1u, u_zero());
             sym_set_tag(S, N, lane, sp - 1u, rtag);
             ++pc; gmin = ngmin; gmax = ngmax; nn = lnn; nc = lnc;
@@ -959,7 +924,7 @@ __global__ __launch_bounds__(256) void k_sym_step(DevLanes L, DevSym S, DevTaint
             // JUMPI pops both words and falls through with its gas by hand and no
             // depth step ("Skipping JUMPI to invalid destination", :1572-1579)
             ++executed;
-            if (kind == K_JUMP) { status = ST_VMEXC; aux = EXC_BADJUMP; break; }
+            if (kind == K_JUMP) { status = MG_VMEXC; aux = MG_EXC_INVALID_JUMP; break; }
             if (gfent[pc] & 2u) fent = pc + 1u;     // _new_node_state on the fall-through
             sp -= 2u; ++pc; gmin += 10u; gmax += 10u;
             continue;
@@ -971,8 +936,8 @@ __global__ __launch_bounds__(256) void k_sym_step(DevLanes L, DevSym S, DevTaint
             // nothing else happens; the table gas, then the OOG check
             const uint64_t ngmin = gmin + (d.x & 0xffffu), ngmax = gmax + (d.x >> 16);
             ++executed;
-            if (flags & LANE_STATIC) { status = ST_VMEXC; aux = EXC_WRITEPROT; break; }
-            if (ngmin >= glim) { status = ST_VMEXC; aux = EXC_OOG; break; }
+            if (flags & MG_LANE_STATIC) { status = MG_VMEXC; aux = MG_EXC_WRITE_PROTECTION; break; }
+            if (ngmin >= glim) { status = MG_VMEXC; aux = MG_EXC_OUT_OF_GAS; break; }
             sp -= npop; ++pc; gmin = ngmin; gmax = ngmax;
             continue;
         }
@@ -986,7 +951,7 @@ __global__ __launch_bounds__(256) void k_sym_step(DevLanes L, DevSym S, DevTaint
             // and nothing is copied; the table gas, then the OOG check
             const uint64_t ngmin = gmin + (d.x & 0xffffu), ngmax = gmax + (d.x >> 16);
             ++executed;
-            if (ngmin >= glim) { status = ST_VMEXC; aux = EXC_OOG; break; }
+            if (ngmin >= glim) { status = MG_VMEXC; aux = MG_EXC_OUT_OF_GAS; break; }
             sp -= 3u; ++pc; gmin = ngmin; gmax = ngmax;
             continue;
         }
@@ -1002,9 +967,9 @@ __global__ __launch_bounds__(256) void k_sym_step(DevLanes L, DevSym S, DevTaint
             // lane ends here too when its modules have no device action on the opcode.
             const uint32_t tlen = sym_tag(S, N, lane, sp - 2u);
             ++executed;
-            if (kind == K_RETURN && !tlen && gmin >= glim) { status = ST_VMEXC; aux = EXC_OOG; break; }
+            if (kind == K_RETURN && !tlen && gmin >= glim) { status = MG_VMEXC; aux = MG_EXC_OUT_OF_GAS; break; }
             L.ret_offset[lane] = 0u; L.ret_len[lane] = MG_RET_SYMBOLIC;
-            status = kind == K_RETURN ? ST_RETURN : ST_REVERT; aux = 0u;
+            status = kind == K_RETURN ? MG_HALT_RETURN : MG_HALT_REVERT; aux = 0u;
             break;
         }
 
@@ -1031,7 +996,7 @@ __global__ __launch_bounds__(256) void k_sym_step(DevLanes L, DevSym S, DevTaint
                     sym_width(S, N, lane, ta) == 1u || sym_width(S, N, lane, tb) == 1u)
                     esc = true;                     // Bool operands, taint lanes: the host
                 else if (!sym_ref(S, N, lane, ta, a, lnc, ya) || !sym_ref(S, N, lane, tb, b, lnc, yb) ||
-                         !sym_node_push(S, N, lane, SYM_BIN | (256u << 8), ya, yb, op, lnn, rtag))
+                         !sym_node_push(S, N, lane, MG_SYM_BIN | (256u << 8), ya, yb, op, lnn, rtag))
                     arena_full = true;
                 else
                     exp_rec = rec_at;
@@ -1039,17 +1004,17 @@ __global__ __launch_bounds__(256) void k_sym_step(DevLanes L, DevSym S, DevTaint
                                                           env_sym || cd_sym)) {
                 esc = true;
             } else if (env_sym) {
-                if (!sym_node_push(S, N, lane, SYM_ENV | (256u << 8), 0u, 0u, envw, lnn, rtag)) arena_full = true;
+                if (!sym_node_push(S, N, lane, MG_SYM_ENV | (256u << 8), 0u, 0u, envw, lnn, rtag)) arena_full = true;
             } else if (op == 0x36u) {
-                if (!sym_node_push(S, N, lane, SYM_CDSIZE | (256u << 8), 0u, 0u, 0u, lnn, rtag)) arena_full = true;
+                if (!sym_node_push(S, N, lane, MG_SYM_CDSIZE | (256u << 8), 0u, 0u, 0u, lnn, rtag)) arena_full = true;
             } else if (op == 0x35u) {
                 if (!sym_ref(S, N, lane, ta, a, lnc, ya) ||
-                    !sym_node_push(S, N, lane, SYM_CDLOAD | (256u << 8), ya, 0u, 0u, lnn, rtag))
+                    !sym_node_push(S, N, lane, MG_SYM_CDLOAD | (256u << 8), ya, 0u, 0u, lnn, rtag))
                     arena_full = true;
             } else if (op == 0x15u || op == 0x19u) {
                 if (op == 0x19u && sym_width(S, N, lane, ta) == 1u) esc = true;   // 2^256-1 - Bool
                 else if (!sym_ref(S, N, lane, ta, a, lnc, ya) ||
-                         !sym_node_push(S, N, lane, SYM_UN | (256u << 8), ya, 0u, op, lnn, rtag))
+                         !sym_node_push(S, N, lane, MG_SYM_UN | (256u << 8), ya, 0u, op, lnn, rtag))
                     arena_full = true;
             } else {
                 // binary: the reference's quirks first (a concrete zero divisor gives
@@ -1062,24 +1027,24 @@ __global__ __launch_bounds__(256) void k_sym_step(DevLanes L, DevSym S, DevTaint
                 else if (op == 0x14u && ta && tb && sym_same(S.node, S.cval, N, lane, ta - 1u, tb - 1u))
                     rval = u_small(1u);     // x == x: the expression layer folds it (expr._fold), If(True, 1, 0)
                 else if (!sym_ref(S, N, lane, ta, a, lnc, ya) || !sym_ref(S, N, lane, tb, b, lnc, yb) ||
-                         !sym_node_push(S, N, lane, SYM_BIN | ((sym_is_cmp(op) ? 1u : 256u) << 8), ya, yb, op,
+                         !sym_node_push(S, N, lane, MG_SYM_BIN | ((sym_is_cmp(op) ? 1u : 256u) << 8), ya, yb, op,
                                         lnn, rtag))
                     arena_full = true;
             }
             // StateTransition: table gas after the mutator, OOG, then the push
             const uint32_t nsp = sp - npop;
             const uint64_t ngmin = gmin + (d.x & 0xffffu), ngmax = gmax + (d.x >> 16);
-            uint32_t stop = ST_RUNNING, sx = 0u;
-            if (esc) { stop = ST_ESCAPE; sx = op | (ESC_SYMBOLIC << 8); }
-            else if (fork) { stop = ST_FORK; sx = op; }
-            else if (arena_full) { stop = ST_ESCAPE; sx = op | (ESC_ARENA << 8); }
-            else if (pushes && nsp + 1u > STACK_LIMIT) { stop = ST_VMEXC; sx = EXC_OVERFLOW; }
-            else if (pushes && nsp + 1u > L.stack_cap) { stop = ST_ESCAPE; sx = op | (ESC_STACK << 8); }
-            else if (ngmin >= glim) { stop = ST_VMEXC; sx = EXC_OOG; }
-            if (stop != ST_RUNNING) {
+            uint32_t stop = MG_RUNNING, sx = 0u;
+            if (esc) { stop = MG_ESCAPE; sx = op | (MG_ESC_SYMBOLIC << 8); }
+            else if (fork) { stop = MG_FORK; sx = op; }
+            else if (arena_full) { stop = MG_ESCAPE; sx = op | (MG_ESC_ARENA << 8); }
+            else if (pushes && nsp + 1u > MG_STACK_LIMIT) { stop = MG_VMEXC; sx = MG_EXC_STACK_OVERFLOW; }
+            else if (pushes && nsp + 1u > L.stack_cap) { stop = MG_ESCAPE; sx = op | (MG_ESC_STACK << 8); }
+            else if (ngmin >= glim) { stop = MG_VMEXC; sx = MG_EXC_OUT_OF_GAS; }
+            if (stop != MG_RUNNING) {
                 if (rec_pre) L.rec_len[lane] = rec_save;   // the instruction did not run
                 // a VmException counts as an executed step, as in k_lane_step
-                if (stop != ST_ESCAPE && stop != ST_FORK) ++executed;
+                if (stop != MG_ESCAPE && stop != MG_FORK) ++executed;
                 status = stop; aux = sx; break;
             }
             if (tl)
@@ -1093,7 +1058,7 @@ __global__ __launch_bounds__(256) void k_sym_step(DevLanes L, DevSym S, DevTaint
             V.set_stack(nsp, rval);
             sym_set_tag(S, N, lane, nsp, rtag);
             sp = nsp + 1u; ++pc; gmin = ngmin; gmax = ngmax; nn = lnn; nc = lnc;
-            if (pre_bit) { ++natoms; if (tact & T_YCLASS) tym |= pre_bit; }
+            if (pre_bit) { ++natoms; if (tact & MG_TAINT_YCLASS) tym |= pre_bit; }
             ++executed;
             continue;
         }
@@ -1110,17 +1075,17 @@ __global__ __launch_bounds__(256) void k_sym_step(DevLanes L, DevSym S, DevTaint
         const uint32_t sp0 = sp;
         slow_step(R, E, uy, d.x);
         n_sha3 = R.n_sha3; n_exp = R.n_exp;
-        if (R.stop != ST_RUNNING) {
+        if (R.stop != MG_RUNNING) {
             if (rec_pre) {
                 // the mutator's own record (EXP) was not published either; drop ours
                 L.rec_len[lane] = rec_save;
             }
             // halts and VmExceptions count as executed steps (k_lane_step: only an
             // escape leaves the instruction unexecuted)
-            if (R.stop != ST_ESCAPE) ++executed;
+            if (R.stop != MG_ESCAPE) ++executed;
             status = R.stop; aux = R.sx; break;
         }
-        if (symlane && (lflags & LANE_MEMTAG) && (kind == K_CDCOPY || kind == K_CODECOPY)) {
+        if (symlane && (lflags & MG_LANE_MEMTAG) && (kind == K_CDCOPY || kind == K_CODECOPY)) {
             // the bytes a copy wrote are concrete now (CODECOPY stops at the end of
             // the code: the bytes after it keep what they held, symbolic or not)
             const U256 c = V.stack(sp0 - 3u);
@@ -1147,10 +1112,10 @@ __global__ __launch_bounds__(256) void k_sym_step(DevLanes L, DevSym S, DevTaint
                 // the post hooks run before manage_cfg: the name before this instruction
                 rec_annot(L, lane, at, natoms + (pre_bit ? 1u : 0u), L.steps[lane] + executed, R.T0,
                           R.sp >= 2u ? R.T1 : u_zero(), pc, op | 0x100u, fent);
-                L.rec_len[lane] = at + TREC_WORDS;
+                L.rec_len[lane] = at + MG_REC_ANNOT_WORDS;
             }
-            if (pre_bit) { ++natoms; if (tact & T_YCLASS) tym |= pre_bit; }
-            if (post_bit) { ++natoms; if (tact & T_YCLASS) tym |= post_bit; }
+            if (pre_bit) { ++natoms; if (tact & MG_TAINT_YCLASS) tym |= pre_bit; }
+            if (post_bit) { ++natoms; if (tact & MG_TAINT_YCLASS) tym |= post_bit; }
         }
         pc = R.pc; sp = R.sp; msize = R.msize; depth = R.depth; gmin = R.gmin; gmax = R.gmax; fent = R.fent;
         ++executed;
@@ -1161,7 +1126,7 @@ __global__ __launch_bounds__(256) void k_sym_step(DevLanes L, DevSym S, DevTaint
     L.gas_min[lane] = gmin; L.gas_max[lane] = gmax;
     L.status[lane] = status; L.aux[lane] = aux;
     L.fent[lane] = fent;
-    if (hook_ack && executed > 0u) lflags &= ~LANE_HOOK_ACK;
+    if (hook_ack && executed > 0u) lflags &= ~MG_LANE_HOOK_ACK;
     if (lflags != flags) L.flags[lane] = lflags;
     L.steps[lane] += executed;
     if (loop_on) L.trace_len[lane] = tlen;
@@ -1175,10 +1140,10 @@ __global__ __launch_bounds__(256) void k_sym_step(DevLanes L, DevSym S, DevTaint
     if (ctr) {
         DevCounters *c = ctr + lane / lanes_pb;
         atomicAdd(&c->lane_steps, (unsigned long long)executed);
-        if (status != ST_RUNNING) {
+        if (status != MG_RUNNING) {
             atomicSub(&c->running, 1u);
-            if (status == ST_HOOK) atomicAdd(&c->hooked, 1u);
-            else if (status == ST_ESCAPE || status == ST_FORK) atomicAdd(&c->escaped, 1u);
+            if (status == MG_HOOK) atomicAdd(&c->hooked, 1u);
+            else if (status == MG_ESCAPE || status == MG_FORK) atomicAdd(&c->escaped, 1u);
             else atomicAdd(&c->halted, 1u);
         }
     }

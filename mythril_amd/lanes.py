@@ -17,11 +17,8 @@ from typing import Dict, Iterable, Optional, Sequence
 
 import numpy as np
 
-# ---- constants mirrored from include/mythgpu.h -------------------------------
-MG_RUNNING, MG_HALT_STOP, MG_HALT_RETURN, MG_HALT_REVERT = 0, 1, 2, 3
-MG_HALT_END, MG_HALT_DROPPED, MG_VMEXC, MG_HOOK, MG_ESCAPE, MG_DEPTH = 4, 5, 6, 7, 8, 9
-MG_LOOP_BOUND = 10
-MG_FORK = 11            # JUMPI on a symbolic condition (symbolic lanes)
+from .abi import *  # noqa: F401,F403  every MG_* constant of include/mythgpu.h
+
 STATUS_NAMES = {
     MG_RUNNING: "running", MG_HALT_STOP: "stop", MG_HALT_RETURN: "return",
     MG_HALT_REVERT: "revert", MG_HALT_END: "end", MG_HALT_DROPPED: "dropped",
@@ -30,49 +27,9 @@ STATUS_NAMES = {
 }
 # statuses after which the reference keeps the world state (svm.py:384-389, 452-460)
 WORLD_STATE_KEPT = (MG_HALT_STOP, MG_HALT_RETURN, MG_HALT_END)
-
-MG_EXC_STACK_UNDERFLOW, MG_EXC_STACK_OVERFLOW, MG_EXC_INVALID_JUMP = 1, 2, 3
-MG_EXC_INVALID_INSTRUCTION, MG_EXC_OUT_OF_GAS, MG_EXC_WRITE_PROTECTION = 4, 5, 6
-MG_ESC_OPCODE, MG_ESC_MEMORY, MG_ESC_STORAGE, MG_ESC_STACK, MG_ESC_TRACE = 1, 2, 3, 4, 5
-MG_ESC_RECORD = 6
-MG_ESC_SYMBOLIC, MG_ESC_ARENA, MG_ESC_TAINT = 7, 8, 9
-MG_RET_SYMBOLIC = 0xFFFFFFFF
-MG_FENT_NONE = 0xFFFFFFFF   # no JUMP / JUMPI landed on a function entry since the upload
-# function-manager records (include/mythgpu.h MG_REC_*)
-MG_REC_KECCAK, MG_REC_EXP, MG_REC_ANNOT, MG_REC_HOOK, MG_REC_HEADER = 1, 2, 3, 4, 11
-MG_REC_SYMKECCAK = 5    # SHA3 of a symbolic input: payload = the KECCAK node's index
-MG_REC_CDSIZE = 6       # a creation's CODESIZE: the host appends calldata.size == result
-MG_REC_SYMEXP = 7       # EXP with a symbolic operand: payload = the Power node's index
-MG_REC_SYMLEN = 8       # SHA3 of a symbolic length: payload = the length's node; host appends len == 64
-MG_REC_ANNOT_WORDS = MG_REC_HEADER + 11
-
-MG_LANE_STATIC, MG_LANE_CREATION, MG_LANE_HOOK_ACK, MG_LANE_STEP1 = 1, 2, 4, 8
-MG_LANE_SYMBOLIC, MG_LANE_SYMCD, MG_LANE_SYMENV_SHIFT = 16, 32, 6
-MG_SYM_CDLOAD, MG_SYM_CDSIZE, MG_SYM_ENV, MG_SYM_BIN, MG_SYM_UN = 1, 2, 3, 4, 5
-MG_SYM_SLOAD, MG_SYM_KECCAK, MG_SYM_EXTRACT, MG_SYM_CONCAT, MG_SYM_TERM = 6, 7, 8, 9, 10
-MG_SYM_CDBYTE = 12      # calldata[w]: one byte of a symbolic calldata copy
-MG_SYM_CDBYTEX = 13     # calldata[simplify(y + w)]: a copy from a symbolic calldata offset
-MG_SYM_MSTOREK = 14     # event: write of value ref z at symbolic offset y (w: 1 word, 2 low byte, 3 byte)
-MG_SYM_MLOADK = 15      # get_word_at(y) over the byte map of the events before it
-MG_SYM_BALANCE = 16     # balance_ of the address ref y over the world state's accounts
-MG_LANE_SYMSTORE, MG_LANE_MEMTAG = 4096, 8192
-MG_LANE_SYMBAL, MG_LANE_SYMRDS, MG_LANE_BALANCE = 32768, 65536, 131072
-MG_ENV_SELFBALANCE, MG_ENV_RETURNDATASIZE, MG_ENV_GAS = 5, 6, 7
-MG_ENV_COINBASE, MG_ENV_TIMESTAMP, MG_ENV_DIFFICULTY, MG_ENV_NUMBER, MG_ENV_CHAINID = 8, 9, 10, 11, 12
-MG_LANE_SYMBLOCK = 262144
-MG_LANE_RETDATA = 16384
-MG_SYM_CONST = 0x80000000
-MG_LANE_TAINT = 2048
-# taint action word (include/mythgpu.h MG_TAINT_*)
-MG_TAINT_POST, MG_TAINT_EXPCOND, MG_TAINT_YCLASS = 16, 32, 64
-MG_TAINT_SINK_SHIFT, MG_TAINT_YIELD_SHIFT = 8, 12
-MG_TAINT_DEFER_SHIFT, MG_TAINT_IFSYM_SHIFT, MG_TAINT_IFLANE = 16, 20, 1 << 24
-MG_TAINT_OBJ0 = 7
-MG_TAINT_CDSIZE = 6     # handle of the symbolic calldata-size object
-ENV_ADDRESS, ENV_CALLER, ENV_ORIGIN, ENV_CALLVALUE, ENV_GASPRICE = range(5)
-MG_ENV_WORDS = 5
-MG_STACK_LIMIT = 1024
-MSTATE_GAS_LIMIT = 1_000_000_000
+ENV_ADDRESS, ENV_CALLER, ENV_ORIGIN, ENV_CALLVALUE, ENV_GASPRICE = (
+    MG_ENV_ADDRESS, MG_ENV_CALLER, MG_ENV_ORIGIN, MG_ENV_CALLVALUE, MG_ENV_GASPRICE)
+MSTATE_GAS_LIMIT = MG_MSTATE_GAS_LIMIT
 
 M256 = (1 << 256) - 1
 

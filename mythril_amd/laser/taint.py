@@ -45,13 +45,14 @@ from typing import Callable, Dict, List, Optional, Tuple
 
 import numpy as np
 
+from .. import abi
 from ..lanes import (MG_TAINT_CDSIZE, MG_TAINT_DEFER_SHIFT, MG_TAINT_EXPCOND, MG_TAINT_IFLANE,
                      MG_TAINT_IFSYM_SHIFT, MG_TAINT_OBJ0, MG_TAINT_POST, MG_TAINT_SINK_SHIFT, MG_TAINT_YCLASS,
                      MG_TAINT_YIELD_SHIFT)
 from ..smt.expr import Expression, symbol_factory
 from .opcodes import OPCODES
 
-MAX_ATOMS = 64
+MAX_ATOMS = abi.MG_TAINT_MAX_ATOMS
 _ENV_ATTRS = ("address", "sender", "origin", "callvalue", "gasprice")     # handles 1..5 (MG_ENV_k + 1)
 
 

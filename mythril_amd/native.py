@@ -12,14 +12,16 @@ import os
 import subprocess
 from pathlib import Path
 
+from . import abi
+from .abi import (MG_OK, MG_EINVAL, MG_EDEVICE, MG_ENOMEM, MG_ESTATE, MG_ENOCODE,  # noqa: F401
+                  MG_EUNSUPPORTED)
+
 PKG_DIR = Path(__file__).resolve().parent
 CSRC = PKG_DIR / "csrc"
 LIB_PATH = PKG_DIR / "libmythgpu.so"
-INCLUDE = PKG_DIR.parent / "include"
+INCLUDE = abi.HEADER.parent
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
-
-MG_OK, MG_EINVAL, MG_EDEVICE, MG_ENOMEM, MG_ESTATE, MG_ENOCODE, MG_EUNSUPPORTED = 0, -1, -2, -3, -4, -5, -6
 
 
 class MythGpuError(RuntimeError):
@@ -27,8 +29,7 @@ class MythGpuError(RuntimeError):
 
 
 def sources():
-    return sorted(CSRC.glob("*.hip")) + sorted(CSRC.glob("*.cuh")) + sorted(CSRC.glob("*.h")) + [
-        INCLUDE / "mythgpu.h"]
+    return sorted(CSRC.glob("*.hip")) + sorted(CSRC.glob("*.cuh")) + sorted(CSRC.glob("*.h")) + [abi.HEADER]
 
 
 HASH_PATH = LIB_PATH.with_name(LIB_PATH.name + ".sha256")

@@ -21,6 +21,7 @@ from typing import Dict, List, Sequence, Tuple
 
 import numpy as np
 
+from .. import abi
 from .expr import Bool, Node, TRUE
 from .lower import Lowering, Unsupported
 from .program import (MAX_SLOTS, OPCODE, REF_ACC, REF_CONST, REF_SLOT, REF_VAR, TAB_LO_SHIFT,
@@ -319,7 +320,7 @@ class NativeCompiler(PyCompiler):
     one call.  Lowering (arrays, uninterpreted functions, wide values ->
     256-bit ops and table lookups) stays in lower.py."""
 
-    _VAR, _CONST, _BAD = 0x1000, 0x1001, 0xFFFF
+    _VAR, _CONST, _BAD = abi.MG_CC_VAR, abi.MG_CC_CONST, 0xFFFF
 
     def __init__(self):
         super().__init__()

@@ -14,23 +14,22 @@ from typing import Dict, List, Optional
 
 import numpy as np
 
-OPS = ["copy", "bvadd", "bvsub", "bvmul", "bvudiv", "bvurem", "bvsdiv", "bvsrem", "bvsmod",
-       "bvand", "bvor", "bvxor", "bvnot", "bvneg", "bvshl", "bvlshr", "bvashr",
-       "eq", "bvult", "bvule", "bvugt", "bvuge", "bvslt", "bvsle", "bvsgt", "bvsge",
-       "and", "or", "xor", "not", "implies", "ite", "extract", "concat", "zero_extend",
-       "sign_extend", "bvadd_noovfl_u", "bvumul_noovfl", "bvsub_noudfl_u", "distinct", "tab",
-       # compiler-internal: ite(cmp(x, y), x, y) folded by flatten._fold_select
-       "bvumin", "bvumax", "bvsmin", "bvsmax",
-       # compiler-internal operand-swapped forms (the accumulator is only ever
-       # operand A, bv_eval.cuh): bvrsub(a, b) = b - a; rconcat(a, b) = concat(b, a)
-       # with the immediate the width of a
-       "bvrsub", "rconcat"]
+from .. import abi
+
+# kernel 2's opcodes by their names in the expression layer, in opcode order; among
+# them the compiler's own: bvumin .. bvsmax = ite(cmp(x, y), x, y) folded by
+# flatten._fold_select, and the operand-swapped forms (the accumulator is only
+# ever operand A): bvrsub(a, b) = b - a; rconcat(a, b) = concat(b, a) with the
+# immediate the width of a
+OPS = [host for _, host in abi.BV_OPS]
 OPCODE = {name: i for i, name in enumerate(OPS)}
 UNARY = {"copy", "bvnot", "bvneg", "not", "extract", "zero_extend", "sign_extend"}
-REF_ACC, REF_SLOT, REF_VAR, REF_CONST = 0, 1, 2, 3
-TAB_PART_SHIFT, TAB_LO_SHIFT, TAB_INDEX_MASK = 20, 21, (1 << 20) - 1
-MAX_SLOTS = 16       # kernel 2's 4-bit slot field (BV_MAX_SLOTS)
-TILE_INSNS = 2048
+REF_ACC, REF_SLOT, REF_VAR, REF_CONST = (
+    abi.MG_BV_REF_ACC, abi.MG_BV_REF_SLOT, abi.MG_BV_REF_VAR, abi.MG_BV_REF_CONST)
+TAB_PART_SHIFT, TAB_LO_SHIFT, TAB_INDEX_MASK = (
+    abi.MG_BV_TAB_PART_SHIFT, abi.MG_BV_TAB_LO_SHIFT, abi.MG_BV_TAB_INDEX_MASK)
+MAX_SLOTS = abi.MG_BV_MAX_SLOTS       # kernel 2's 4-bit slot field
+TILE_INSNS = abi.MG_BV_TILE_INSNS
 
 
 # operand references per op (bv_upload: ite 3, one-operand ops 1, the rest 2)

@@ -36,12 +36,13 @@ from typing import Callable, Dict, Iterable, List, Optional, Sequence
 
 import numpy as np
 
+from .. import abi
 from .expr import And, BitVec, Bool, Node, TRUE, _fold, _select, const, symbol_factory
 from .flatten import Compiler, batch_from, compile_sets
 from .lower import Unsupported
 from .program import ArrayInterp, FuncInterp, ModelPool, PoolColumns, compact_vars, concat_pools, read_sets
 
-NO_MODEL = 0xFFFFFFFF
+NO_MODEL = abi.MG_BV_NO_MODEL
 
 
 class UnsatError(Exception):

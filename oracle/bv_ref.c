@@ -10,21 +10,13 @@
  * most-recently-used order (UINT32_MAX if none) and the satisfying count.
  *
  * Independent of the device code: 4 x u64 limbs (u256_ref.h) and its own
- * decoder; only the instruction format is shared.
+ * decoder; only the instruction format (include/mythgpu.h MG_BV_*) is shared.
  */
 #include <pthread.h>
 #include <stdint.h>
 #include <string.h>
 #include "u256_ref.h"
-
-enum {
-    OP_COPY = 0, OP_ADD, OP_SUB, OP_MUL, OP_UDIV, OP_UREM, OP_SDIV, OP_SREM, OP_SMOD,
-    OP_AND, OP_OR, OP_XOR, OP_NOT, OP_NEG, OP_SHL, OP_LSHR, OP_ASHR,
-    OP_EQ, OP_ULT, OP_ULE, OP_UGT, OP_UGE, OP_SLT, OP_SLE, OP_SGT, OP_SGE,
-    OP_BAND, OP_BOR, OP_BXOR, OP_BNOT, OP_BIMPLIES, OP_ITE, OP_EXTRACT, OP_CONCAT,
-    OP_ZEXT, OP_SEXT, OP_ADD_NOOVF_U, OP_MUL_NOOVF_U, OP_SUB_NOUDF_U, OP_NE, OP_TAB,
-    OP_UMIN, OP_UMAX, OP_SMIN, OP_SMAX, OP_RSUB, OP_RCONCAT
-};
+#include "../include/mythgpu.h"
 
 static u256 w_mask(u256 v, unsigned w) {
     if (w >= 256) return v;
@@ -60,7 +52,8 @@ typedef struct {
 /* Value of table `imm` (index | part << 20 | lo << 21) at key (k0, k1) in model m:
  * the listed entry with that key, else the default; bits [256 part + lo, ...). */
 static u256 table_lookup(const job_t *j, u256 k0, u256 k1, uint32_t imm, uint32_t m) {
-    const uint32_t t = imm & 0xfffffu, part = (imm >> 20) & 1u, lo = (imm >> 21) & 0xffu;
+    const uint32_t t = imm & MG_BV_TAB_INDEX_MASK, part = (imm >> MG_BV_TAB_PART_SHIFT) & 1u,
+                   lo = (imm >> MG_BV_TAB_LO_SHIFT) & 0xffu;
     const size_t tm = (size_t)t * j->n_models + m;
     u256 v = u_from_limbs32(j->tab->dflt + tm * 16 + part * 8);
     for (uint32_t k = 0; k < j->tab->count[tm]; ++k) {
@@ -84,7 +77,7 @@ static u256 fetch(const job_t *j, u256 acc, const u256 *slots, uint32_t ref, uin
 }
 
 static int eval_one(const job_t *j, uint32_t d, uint32_t m) {
-    u256 slots[16];
+    u256 slots[MG_BV_MAX_SLOTS];
     memset(slots, 0, sizeof slots);
     u256 acc = u_zero();
     for (uint32_t p = j->prog_off[d]; p < j->prog_off[d + 1]; ++p) {
@@ -92,60 +85,60 @@ static int eval_one(const job_t *j, uint32_t d, uint32_t m) {
         uint32_t op = w[0] & 0xff, width = (w[0] >> 8) & 0x1ff;
         u256 a = fetch(j, acc, slots, w[1], m), r;
         u256 b = u_zero(), c = u_zero();
-        int unary = op == OP_COPY || op == OP_NOT || op == OP_NEG || op == OP_BNOT ||
-                    op == OP_EXTRACT || op == OP_ZEXT || op == OP_SEXT;
+        int unary = op == MG_BV_COPY || op == MG_BV_NOT || op == MG_BV_NEG || op == MG_BV_BNOT ||
+                    op == MG_BV_EXTRACT || op == MG_BV_ZEXT || op == MG_BV_SEXT;
         if (!unary) b = fetch(j, acc, slots, w[2], m);
-        if (op == OP_ITE) c = fetch(j, acc, slots, w[3], m);
+        if (op == MG_BV_ITE) c = fetch(j, acc, slots, w[3], m);
         unsigned ow = w[3];  /* operand width for compares / concat low width */
         switch (op) {
-        case OP_COPY: case OP_ZEXT: r = a; break;
-        case OP_ADD: r = u_add(a, b); break;
-        case OP_SUB: r = u_sub(a, b); break;
-        case OP_MUL: r = u_mul(a, b); break;
-        case OP_UDIV: r = u_is_zero(b) ? w_mask(u_not(u_zero()), width) : z_udiv(a, b); break;
-        case OP_UREM: r = z_urem(a, b); break;
-        case OP_SDIV: r = z_sdiv(w_sext(a, width), w_sext(b, width)); break;
-        case OP_SREM: r = z_srem(w_sext(a, width), w_sext(b, width)); break;
-        case OP_SMOD: r = z_smod(w_sext(a, width), w_sext(b, width)); break;
-        case OP_AND: r = u_and(a, b); break;
-        case OP_OR: r = u_or(a, b); break;
-        case OP_XOR: r = u_xor(a, b); break;
-        case OP_NOT: r = u_not(a); break;
-        case OP_NEG: r = u_negate(a); break;
-        case OP_SHL: r = (u_fits64(b) && b.w[0] < width) ? u_shl(a, b) : u_zero(); break;
-        case OP_LSHR: r = (u_fits64(b) && b.w[0] < width) ? u_lshr(a, b) : u_zero(); break;
-        case OP_ASHR: {
+        case MG_BV_COPY: case MG_BV_ZEXT: r = a; break;
+        case MG_BV_ADD: r = u_add(a, b); break;
+        case MG_BV_SUB: r = u_sub(a, b); break;
+        case MG_BV_MUL: r = u_mul(a, b); break;
+        case MG_BV_UDIV: r = u_is_zero(b) ? w_mask(u_not(u_zero()), width) : z_udiv(a, b); break;
+        case MG_BV_UREM: r = z_urem(a, b); break;
+        case MG_BV_SDIV: r = z_sdiv(w_sext(a, width), w_sext(b, width)); break;
+        case MG_BV_SREM: r = z_srem(w_sext(a, width), w_sext(b, width)); break;
+        case MG_BV_SMOD: r = z_smod(w_sext(a, width), w_sext(b, width)); break;
+        case MG_BV_AND: r = u_and(a, b); break;
+        case MG_BV_OR: r = u_or(a, b); break;
+        case MG_BV_XOR: r = u_xor(a, b); break;
+        case MG_BV_NOT: r = u_not(a); break;
+        case MG_BV_NEG: r = u_negate(a); break;
+        case MG_BV_SHL: r = (u_fits64(b) && b.w[0] < width) ? u_shl(a, b) : u_zero(); break;
+        case MG_BV_LSHR: r = (u_fits64(b) && b.w[0] < width) ? u_lshr(a, b) : u_zero(); break;
+        case MG_BV_ASHR: {
             u256 sa = w_sext(a, width);
             r = (u_fits64(b) && b.w[0] < width) ? u_ashr(sa, b) : u_ashr(sa, u_from64(255));
             break;
         }
-        case OP_EQ: r = w_bool(u_eq(a, b)); break;
-        case OP_NE: r = w_bool(!u_eq(a, b)); break;
-        case OP_ULT: r = w_bool(u_lt(a, b)); break;
-        case OP_ULE: r = w_bool(!u_lt(b, a)); break;
-        case OP_UGT: r = w_bool(u_lt(b, a)); break;
-        case OP_UGE: r = w_bool(!u_lt(a, b)); break;
-        case OP_SLT: r = w_bool(u_slt(w_sext(a, ow), w_sext(b, ow))); break;
-        case OP_SLE: r = w_bool(!u_slt(w_sext(b, ow), w_sext(a, ow))); break;
-        case OP_SGT: r = w_bool(u_slt(w_sext(b, ow), w_sext(a, ow))); break;
-        case OP_SGE: r = w_bool(!u_slt(w_sext(a, ow), w_sext(b, ow))); break;
-        case OP_BAND: r = w_bool((a.w[0] & b.w[0]) & 1); break;
-        case OP_BOR: r = w_bool((a.w[0] | b.w[0]) & 1); break;
-        case OP_BXOR: r = w_bool((a.w[0] ^ b.w[0]) & 1); break;
-        case OP_BNOT: r = w_bool(!(a.w[0] & 1)); break;
-        case OP_BIMPLIES: r = w_bool(!(a.w[0] & 1) || (b.w[0] & 1)); break;
-        case OP_ITE: r = (a.w[0] & 1) ? b : c; break;
-        case OP_EXTRACT: r = u_lshr(a, u_from64(w[2] & 0xff)); break;
-        case OP_CONCAT: r = u_or(u_shl(a, u_from64(ow)), b); break;
-        case OP_SEXT: r = w_sext(a, w[2]); break;
-        case OP_ADD_NOOVF_U: {
+        case MG_BV_EQ: r = w_bool(u_eq(a, b)); break;
+        case MG_BV_NE: r = w_bool(!u_eq(a, b)); break;
+        case MG_BV_ULT: r = w_bool(u_lt(a, b)); break;
+        case MG_BV_ULE: r = w_bool(!u_lt(b, a)); break;
+        case MG_BV_UGT: r = w_bool(u_lt(b, a)); break;
+        case MG_BV_UGE: r = w_bool(!u_lt(a, b)); break;
+        case MG_BV_SLT: r = w_bool(u_slt(w_sext(a, ow), w_sext(b, ow))); break;
+        case MG_BV_SLE: r = w_bool(!u_slt(w_sext(b, ow), w_sext(a, ow))); break;
+        case MG_BV_SGT: r = w_bool(u_slt(w_sext(b, ow), w_sext(a, ow))); break;
+        case MG_BV_SGE: r = w_bool(!u_slt(w_sext(a, ow), w_sext(b, ow))); break;
+        case MG_BV_BAND: r = w_bool((a.w[0] & b.w[0]) & 1); break;
+        case MG_BV_BOR: r = w_bool((a.w[0] | b.w[0]) & 1); break;
+        case MG_BV_BXOR: r = w_bool((a.w[0] ^ b.w[0]) & 1); break;
+        case MG_BV_BNOT: r = w_bool(!(a.w[0] & 1)); break;
+        case MG_BV_BIMPLIES: r = w_bool(!(a.w[0] & 1) || (b.w[0] & 1)); break;
+        case MG_BV_ITE: r = (a.w[0] & 1) ? b : c; break;
+        case MG_BV_EXTRACT: r = u_lshr(a, u_from64(w[2] & 0xff)); break;
+        case MG_BV_CONCAT: r = u_or(u_shl(a, u_from64(ow)), b); break;
+        case MG_BV_SEXT: r = w_sext(a, w[2]); break;
+        case MG_BV_ADD_NOOVF_U: {
             /* z3 bvadd_noovfl (unsigned): the (w+1)-bit sum has a zero top bit */
             u256 s = u_add(a, b);
             int ovf = ow >= 256 ? u_lt(s, a) : !u_is_zero(u_lshr(s, u_from64(ow)));
             r = w_bool(!ovf);
             break;
         }
-        case OP_MUL_NOOVF_U: {
+        case MG_BV_MUL_NOOVF_U: {
             /* z3 bvumul_noovfl: the high w bits of the 2w-bit product are zero.
              * Computed exactly with a 512-bit product. */
             uint64_t prod[8] = {0};
@@ -163,14 +156,14 @@ static int eval_one(const job_t *j, uint32_t d, uint32_t m) {
             r = w_bool(!ovf);
             break;
         }
-        case OP_SUB_NOUDF_U: r = w_bool(!u_lt(a, b)); break;
-        case OP_TAB: r = table_lookup(j, a, b, w[3], m); break;
-        case OP_UMIN: r = u_lt(b, a) ? b : a; break;
-        case OP_UMAX: r = u_lt(a, b) ? b : a; break;
-        case OP_SMIN: r = u_slt(w_sext(b, width), w_sext(a, width)) ? b : a; break;
-        case OP_SMAX: r = u_slt(w_sext(a, width), w_sext(b, width)) ? b : a; break;
-        case OP_RSUB: r = u_sub(b, a); break;
-        case OP_RCONCAT: r = u_or(u_shl(b, u_from64(ow)), a); break;   /* a low (ow bits), b high */
+        case MG_BV_SUB_NOUDF_U: r = w_bool(!u_lt(a, b)); break;
+        case MG_BV_TAB: r = table_lookup(j, a, b, w[3], m); break;
+        case MG_BV_UMIN: r = u_lt(b, a) ? b : a; break;
+        case MG_BV_UMAX: r = u_lt(a, b) ? b : a; break;
+        case MG_BV_SMIN: r = u_slt(w_sext(b, width), w_sext(a, width)) ? b : a; break;
+        case MG_BV_SMAX: r = u_slt(w_sext(a, width), w_sext(b, width)) ? b : a; break;
+        case MG_BV_RSUB: r = u_sub(b, a); break;
+        case MG_BV_RCONCAT: r = u_or(u_shl(b, u_from64(ow)), a); break;   /* a low (ow bits), b high */
         default: r = u_zero(); break;
         }
         r = w_mask(r, width);
@@ -183,11 +176,11 @@ static int eval_one(const job_t *j, uint32_t d, uint32_t m) {
 static void *worker(void *arg) {
     job_t *j = (job_t *)arg;
     for (uint32_t d = j->d0; d < j->d1; ++d) {
-        uint32_t first = 0xffffffffu, cnt = 0;
+        uint32_t first = MG_BV_NO_MODEL, cnt = 0;
         const uint32_t words = (j->n_models + 63u) / 64u;
         for (uint32_t m = 0; m < j->n_models; ++m)
             if (eval_one(j, d, m)) {
-                if (first == 0xffffffffu) first = m;
+                if (first == MG_BV_NO_MODEL) first = m;
                 ++cnt;
                 if (j->bits) j->bits[(size_t)d * words + m / 64u] |= 1ull << (m % 64u);
             }
