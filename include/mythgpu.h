@@ -227,7 +227,11 @@ extern "C" {
 
 /* ------------------------------------------------------- host lane layout */
 /* Lane-major host image of a batch of concrete EVM paths.  Any pointer may be
- * NULL on download to skip that field.                                     */
+ * NULL on download to skip that field; mg_lanes_download_live bounds rows by
+ * their count array, so there a row field that is requested (non-NULL, with a
+ * non-zero capacity) needs its count: sp for stack, storage_count for storage,
+ * msize for memory, trace_len for trace, rec_len for rec (else MG_EINVAL).
+ * An upload reads every array (only fent may be NULL).                      */
 typedef struct mg_lane_soa {
     uint32_t n;             /* lanes described by the arrays below            */
     uint32_t stack_cap;     /* stack entries per lane in `stack`              */
@@ -350,6 +354,7 @@ typedef struct mg_ctx mg_ctx;
                              the state at the start of the JUMPI (host forks)    */
 
 /* Host image of the symbolic planes of lanes [first, first + n), lane-major.
+ * Every pointer is required, on upload and on download (none may be NULL).
  * Memory bytes and storage entries carry tags too (ABI v7): a memory byte tag is
  * 0 (the byte in `memory` is the value) or 1 + (node << 5 | j): byte j (0 = most
  * significant) of that node's word, i.e. Extract(255 - 8j, 248 - 8j, word) as
@@ -413,7 +418,8 @@ int         mg_sym_download(mg_ctx *ctx, mg_sym_soa *host, uint32_t first, uint3
 #define MG_TAINT_OBJ0        7u  /* first object-table handle                                  */
 #define MG_TAINT_MAX_ATOMS  64u  /* atoms per lane: one bit each of an annotation mask         */
 
-/* Host image of the taint planes of lanes [first, first + n), lane-major. */
+/* Host image of the taint planes of lanes [first, first + n), lane-major.
+ * Every pointer is required, on upload and on download (none may be NULL). */
 typedef struct mg_taint_soa {
     uint32_t n, stack_cap, obj_cap, _pad;
     uint32_t *sobj;         /* [n][stack_cap] object handle per stack slot      */
@@ -473,19 +479,31 @@ int         mg_code_table(mg_ctx *ctx, uint32_t code_id, uint8_t *ops, uint32_t 
 /* ----------------------------------------------------------------- lanes */
 int         mg_lanes_alloc(mg_ctx *ctx, const mg_batch_cfg *cfg);
 /* Upload lanes [first, first+n) from host (host->n must equal n).  The
- * upload also becomes the batch's resident initial image (see mg_lanes_reset). */
+ * upload also becomes the batch's resident initial image (see mg_lanes_reset).
+ * The scalars, calldata and the environment words go whole (up to the host's
+ * calldata_cap); rows go only below the range's largest host count -- stack
+ * below the largest sp, memory below the largest msize, storage below the
+ * largest storage_count, trace / records below the largest trace_len /
+ * rec_len -- and device rows above those bounds, like every lane outside the
+ * range, keep their contents (no step reads them before writing them).  A host
+ * trace_cap / rec_cap of 0 zeroes the range's trace_len / rec_len.            */
 int         mg_lanes_upload(mg_ctx *ctx, const mg_lane_soa *host, uint32_t first, uint32_t n);
 int         mg_lanes_download(mg_ctx *ctx, mg_lane_soa *host, uint32_t first, uint32_t n);
 /* mg_lanes_download of what the lanes can have changed, for a host image that
  * was uploaded from the same buffers: the scalars, then each lane's stack rows
  * below the largest sp of the range, memory below the largest msize, storage
  * entries below the largest storage_count, records below the largest rec_len
- * and trace entries below the largest trace_len.  calldata and the environment
+ * and trace entries below the largest trace_len (the device's counts, clipped
+ * to the host's capacities).  calldata and the environment
  * words (never written by a step) and everything above those bounds keep the
- * host's contents.  The batched LaserEVM's per-launch copy-back
+ * host's contents.  A requested row field whose count array is NULL is refused
+ * with MG_EINVAL (the error names the array) before anything is launched.  The
+ * batched LaserEVM's per-launch copy-back
  * (svm.py:293-337 drain) -- a full download moves every lane's whole stack.  */
 int         mg_lanes_download_live(mg_ctx *ctx, mg_lane_soa *host, uint32_t first, uint32_t n);
-/* mg_lanes_upload of what a step reads: the scalars, calldata and environment
+/* The same transfer as mg_lanes_upload (every upload is bounded by the range's
+ * largest counts since ABI v9's round 4; the name is kept for callers that say
+ * what they rely on): the scalars, calldata and environment
  * words whole, each lane's stack rows below the largest sp of the range,
  * memory below the largest msize (a step zero-fills memory it extends),
  * storage entries below the largest storage_count, trace entries below the

@@ -785,17 +785,18 @@ static int check_host_shape(mg_ctx *ctx, const mg_lane_soa *h, uint32_t first, u
     return MG_OK;
 }
 
-static int lanes_upload(mg_ctx *ctx, const mg_lane_soa *h, uint32_t first, uint32_t n, bool live);
+static int lanes_upload(mg_ctx *ctx, const mg_lane_soa *h, uint32_t first, uint32_t n);
 
 extern "C" int mg_lanes_upload(mg_ctx *ctx, const mg_lane_soa *h, uint32_t first, uint32_t n) {
-    return lanes_upload(ctx, h, first, n, false);
+    return lanes_upload(ctx, h, first, n);
 }
 
+// the same transfer: every upload is bounded by the range's largest counts
 extern "C" int mg_lanes_upload_live(mg_ctx *ctx, const mg_lane_soa *h, uint32_t first, uint32_t n) {
-    return lanes_upload(ctx, h, first, n, true);
+    return lanes_upload(ctx, h, first, n);
 }
 
-static int lanes_upload(mg_ctx *ctx, const mg_lane_soa *h, uint32_t first, uint32_t n, bool live) {
+static int lanes_upload(mg_ctx *ctx, const mg_lane_soa *h, uint32_t first, uint32_t n) {
     if (!ctx) return MG_EINVAL;
     int rc;
     if ((rc = check_host_shape(ctx, h, first, n))) return rc;
@@ -816,7 +817,6 @@ static int lanes_upload(mg_ctx *ctx, const mg_lane_soa *h, uint32_t first, uint3
     for (uint32_t i = 0; i < n && fresh; ++i)
         fresh = h->sp[i] == 0 && h->msize[i] == 0 && (!h->trace_cap || h->trace_len[i] == 0) &&
                 (!h->rec_cap || h->rec_len[i] == 0);
-    const uint32_t ALL = 0xffffffffu;
     XferPlan x(n, first);
     x.scalar(h->code_id, L.code_id, 4);
     x.scalar(h->pc, L.pc, 4, ctx->i_pc);
@@ -838,8 +838,8 @@ static int lanes_upload(mg_ctx *ctx, const mg_lane_soa *h, uint32_t first, uint3
     // rows below the range's largest sp / storage count / msize / trace and record
     // length: no step reads above them before writing (pushes write their slot,
     // stores and logs append, memory is zero-filled when it extends), so the rest
-    // of each capacity never crosses PCIe (`live` only leaves out env and calldata)
-    (void)ALL;
+    // of each capacity never crosses PCIe and the device rows above the bounds keep
+    // their contents; env and calldata go whole (a step reads any byte of them)
     x.units(h->stack, h->stack_cap, 8, L.stack, max_of(h->sp, n));
     x.units(h->env, MG_ENV_WORDS, 8, L.env);
     x.units(h->storage, h->storage_cap, 16, L.storage, max_of(h->storage_count, n), ctx->i_storage);
@@ -1111,6 +1111,19 @@ static int lanes_download(mg_ctx *ctx, mg_lane_soa *h, uint32_t first, uint32_t 
     if ((rc = check_host_shape(ctx, h, first, n))) return rc;
     HIPX(ctx, hipSetDevice(ctx->device));
     DevLanes &L = ctx->L;
+    // live rows are bounded by the downloaded counts: a requested row field whose
+    // count array is skipped (NULL) has no bound
+    if (live) {
+        const struct { const void *rows; uint32_t cap; const void *count; const char *name; } need[] = {
+            {h->stack, h->stack_cap, h->sp, "sp"},
+            {h->storage, h->storage_cap, h->storage_count, "storage_count"},
+            {h->memory, h->mem_cap, h->msize, "msize"},
+            {h->trace, h->trace_cap, h->trace_len, "trace_len"},
+            {h->rec, h->rec_cap, h->rec_len, "rec_len"}};
+        for (const auto &f : need)
+            if (f.rows && f.cap && !f.count)
+                return set_err(ctx, MG_EINVAL, "mg_lanes_download_live: %s is NULL but its rows are requested", f.name);
+    }
     // phase 1: the per-lane scalars (they bound phase 2's rows)
     XferPlan x(n, first);
     x.scalar(h->code_id, L.code_id, 4);
@@ -1136,14 +1149,18 @@ static int lanes_download(mg_ctx *ctx, mg_lane_soa *h, uint32_t first, uint32_t 
     // phase 2: rows; live: only what a step can have written, below the
     // range's largest sp / storage count / msize / trace and record length
     const uint32_t ALL = 0xffffffffu;
+    // a skipped (NULL) row field needs no bound, so its count array may be NULL too
+    auto bound = [&](const void *rows, const uint32_t *count) {
+        return live && rows ? max_of(count, n) : ALL;
+    };
     XferPlan y(n, first);
-    y.units(h->stack, h->stack_cap, 8, L.stack, live ? max_of(h->sp, n) : ALL);
+    y.units(h->stack, h->stack_cap, 8, L.stack, bound(h->stack, h->sp));
     if (!live) y.units(h->env, MG_ENV_WORDS, 8, L.env);
-    y.units(h->storage, h->storage_cap, 16, L.storage, live ? max_of(h->storage_count, n) : ALL);
-    y.bytes(h->memory, h->mem_cap, L.mem, live ? (max_of(h->msize, n) + 3u) / 4u : ALL);
+    y.units(h->storage, h->storage_cap, 16, L.storage, bound(h->storage, h->storage_count));
+    y.bytes(h->memory, h->mem_cap, L.mem, live && h->memory ? (max_of(h->msize, n) + 3u) / 4u : ALL);
     if (!live) y.bytes(h->calldata, h->calldata_cap, L.calldata);
-    if (h->trace_cap) y.units(h->trace, h->trace_cap, 1, L.trace, live ? max_of(h->trace_len, n) : ALL);
-    if (h->rec_cap) y.units(h->rec, h->rec_cap, 1, L.rec, live ? max_of(h->rec_len, n) : ALL);
+    if (h->trace_cap) y.units(h->trace, h->trace_cap, 1, L.trace, bound(h->trace, h->trace_len));
+    if (h->rec_cap) y.units(h->rec, h->rec_cap, 1, L.rec, bound(h->rec, h->rec_len));
     return xfer_down(ctx, y);
 }
 

@@ -150,8 +150,9 @@ class GpuDevice:
 
     def upload_range(self, batch: LaneBatch, first: int, n: int, live: bool = False):
         """Upload lanes [first, first + n) of `batch` to the same device lanes.
-        live=True: only what a step reads, below the range's largest sp /
-        msize / storage count / record and trace length (mg_lanes_upload_live)."""
+        Every upload moves only what a step reads, below the range's largest sp /
+        msize / storage count / record and trace length; live=True says so by
+        name (mg_lanes_upload_live, the same transfer as mg_lanes_upload)."""
         soa = batch.soa_range(first, n)
         fn = self.lib.mg_lanes_upload_live if live else self.lib.mg_lanes_upload
         self._check(fn(self.ctx, ctypes.addressof(soa), first, n),

@@ -21,6 +21,7 @@ from mythril_amd.lanes import (_ALL_FIELDS, _SYM_FIELDS, _TAINT_FIELDS, LaneBatc
 from oracle.evm_ref import OracleEVM
 
 from taintref import run_lane
+from xfermodel import DeviceImage
 
 
 class OracleDevice:
@@ -71,8 +72,18 @@ class OracleDevice:
                 sl = tuple(slice(0, min(x, y)) for x, y in zip(a.shape[1:], b.shape[1:]))
                 a[(slice(first, first + n),) + sl] = b[(slice(first, first + n),) + sl]
 
+    # Transfers move exactly what the device's do (tests/xfermodel.py restates the
+    # contract of mg_lanes_upload / _download and their _live forms): uploads write
+    # rows only below the range's largest counts, live downloads only below the
+    # device's, so host code that relies on data a transfer does not move fails here
+    # as it would on the GPU.
+    def _model(self) -> DeviceImage:
+        m = DeviceImage.__new__(DeviceImage)
+        m.shape, m.img = self._img.shape, self._img
+        return m
+
     def upload(self, batch: LaneBatch, first: int = 0):
-        self._copy(batch, self._img, first, batch.n)
+        self._model().upload(batch, first, batch.n, host_first=0)
         self._init = LaneBatch(self._img.shape)           # the resident initial image
         self._copy(self._img, self._init, 0, self._img.n)
 
@@ -89,13 +100,13 @@ class OracleDevice:
         return out
 
     def download(self, batch: LaneBatch, first: int = 0):
-        self._copy(self._img, batch, first, batch.n)
+        self._model().download(batch, first, batch.n, host_first=0)
 
     def upload_range(self, batch: LaneBatch, first: int, n: int, live: bool = False):
-        self._copy(batch, self._img, first, n)
+        self._model().upload(batch, first, n, live=live)
 
     def download_range(self, batch: LaneBatch, first: int, n: int, live: bool = False):
-        self._copy(self._img, batch, first, n)
+        self._model().download(batch, first, n, live=live)
 
     def set_loop_bound(self, bound: int):
         self._bound = int(bound)
