@@ -628,6 +628,17 @@ static int bv_upload(BvState &s, const mg_dag_batch *dags, const mg_model_batch 
             }
         }
     }
+    // the models' tables too, before anything of the previous upload is replaced: a
+    // refused batch leaves that upload whole (mg_eval_run on it stays valid)
+    if (models->n_tables) {
+        if (!models->tab_start || !models->tab_count || !models->tab_default ||
+            (models->n_entries && !models->tab_entries)) { msg = "table arrays missing"; return MG_EINVAL; }
+        const size_t tm = (size_t)models->n_tables * models->n_models;
+        for (size_t k = 0; k < tm; ++k)
+            if ((uint64_t)models->tab_start[k] + models->tab_count[k] > models->n_entries) {
+                msg = "table entries out of range"; return MG_EINVAL;
+            }
+    }
     const char *fv = getenv("MG_BV_FUSE");
     const uint32_t *insns = dags->insns, *prog_off = dags->prog_off;
     uint32_t total_up = total;
