@@ -981,7 +981,7 @@ __global__ __launch_bounds__(256) void k_sym_step(DevLanes L, DevSym S, DevTaint
             const uint32_t tb = sp >= 2u && nin >= 2u ? sym_tag(S, N, lane, sp - 2u) : 0u;
             uint32_t lnn = nn, lnc = nc, rtag = 0u;
             U256 rval = u_zero();
-            bool esc = false, arena_full = false, fork = false;
+            bool esc = false, arena_full = false, rec_full = false, fork = false;
             uint32_t ya = 0u, yb = 0u;
             uint32_t exp_rec = 0xffffffffu;         // EXP: where its MG_REC_SYMEXP record goes
             if (kind == K_JUMPI) {
@@ -992,9 +992,10 @@ __global__ __launch_bounds__(256) void k_sym_step(DevLanes L, DevSym S, DevTaint
                 // exponent), the uninterpreted function, and the manager's condition
                 // on it appended to the path (the host replays the record in order)
                 const uint32_t rec_at = L.rec_len[lane];
-                if (tl || !L.rec_cap || (uint64_t)rec_at + MG_REC_HEADER + 1u > L.rec_cap ||
-                    sym_width(S, N, lane, ta) == 1u || sym_width(S, N, lane, tb) == 1u)
+                if (tl || !L.rec_cap || sym_width(S, N, lane, ta) == 1u || sym_width(S, N, lane, tb) == 1u)
                     esc = true;                     // Bool operands, taint lanes: the host
+                else if ((uint64_t)rec_at + MG_REC_HEADER + 1u > L.rec_cap)
+                    rec_full = true;                // the host regrows the log and runs the lane again
                 else if (!sym_ref(S, N, lane, ta, a, lnc, ya) || !sym_ref(S, N, lane, tb, b, lnc, yb) ||
                          !sym_node_push(S, N, lane, MG_SYM_BIN | (256u << 8), ya, yb, op, lnn, rtag))
                     arena_full = true;
@@ -1038,6 +1039,7 @@ __global__ __launch_bounds__(256) void k_sym_step(DevLanes L, DevSym S, DevTaint
             if (esc) { stop = MG_ESCAPE; sx = op | (MG_ESC_SYMBOLIC << 8); }
             else if (fork) { stop = MG_FORK; sx = op; }
             else if (arena_full) { stop = MG_ESCAPE; sx = op | (MG_ESC_ARENA << 8); }
+            else if (rec_full) { stop = MG_ESCAPE; sx = op | (MG_ESC_RECORD << 8); }
             else if (pushes && nsp + 1u > MG_STACK_LIMIT) { stop = MG_VMEXC; sx = MG_EXC_STACK_OVERFLOW; }
             else if (pushes && nsp + 1u > L.stack_cap) { stop = MG_ESCAPE; sx = op | (MG_ESC_STACK << 8); }
             else if (ngmin >= glim) { stop = MG_VMEXC; sx = MG_EXC_OUT_OF_GAS; }

@@ -148,9 +148,14 @@ class Engine:
         mem = ms.memory.raw()
         st = env.active_account.storage
         store = {} if st.is_chain else st.printable_storage
+        # concrete calldata of a symbolic state (a symbolic caller or call value): the
+        # oracle reads it; symbolic calldata never reaches the oracle
+        cd = bytes(env.calldata) if isinstance(env.calldata, (bytes, bytearray)) else b""
         shape = LaneShape(n=1, stack_cap=1024, mem_cap=max(4096, (len(mem) + 31) // 32 * 32 + 4096),
-                          calldata_cap=32, storage_cap=max(16, 2 * len(store) + 4))
+                          calldata_cap=max(32, (len(cd) + 31) // 32 * 32), storage_cap=max(16, 2 * len(store) + 4))
         b = LaneBatch(shape)
+        b.calldata[0, :len(cd)] = np.frombuffer(cd, dtype=np.uint8)
+        b.calldata_len[0] = len(cd)
         b.code_id[0] = self._cid(env.code)
         b.pc[0], b.sp[0] = ms.pc, len(stack)
         for k, v in enumerate(stack):
@@ -269,6 +274,10 @@ class Engine:
         the reference's expressions."""
         ms, env = s.mstate, s.environment
         st = ms.stack
+        if op == 0x55 and env.static:
+            # sstore_ is a state mutation: StateTransition raises WriteProtection before
+            # the mutator runs (instructions.py:98-202, 1508-1509)
+            return self._vmexc(state if state is not None else s)
         if op in (0x51, 0x52, 0x53) and _val(st[-1]) is None:
             return self._symbolic_offset(state if state is not None else s, s, op)
         if op == 0x20 and _val(st[-1]) is None:
@@ -507,7 +516,9 @@ class Engine:
             a, b = st.pop(), st.pop()
             res = self._binary(op, a, b)
         if len(st) + 1 > 1024:
-            raise Unsupported("stack overflow")
+            # MachineStack.append raises StackOverflowException, a VmException, in the
+            # mutator: before the gas is added (machine_state.py:29-56)
+            return self._vmexc(state)
         if ms.min_gas_used + gmin >= min(_gas_limit(s), 10 ** 9 + 1):
             return self._vmexc(state)
         if cond_after is not None:
@@ -691,7 +702,7 @@ class Engine:
         if op == 0x38:
             n = code_len + 0x200
             if len(st) + 1 > 1024:
-                raise Unsupported("stack overflow")
+                return self._vmexc(state)      # StackOverflowException (machine_state.py:29-56)
             s.world_state.constraints.append(env.calldata.size == BVV(n, 256))
             st.append(BVV(n, 256))
         else:

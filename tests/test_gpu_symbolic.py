@@ -11,21 +11,15 @@
   outcomes and constraint sequences as the restatement, with the symbolic
   lanes' instructions executed on the device.
 """
-from copy import copy
-
 import pytest
 
 import symcases
+import symcosim
 import symref
 from mythril_amd.device import GpuDevice
-from mythril_amd.lanes import (MG_ESC_SYMBOLIC, MG_ESCAPE, MG_FORK, MG_LANE_SYMBOLIC, MG_RUNNING,
-                               LaneBatch)
-from mythril_amd.laser import (BreadthFirstSearchStrategy, LaserEVM, MessageCallTransaction,
-                               SymbolicCalldata)
+from mythril_amd.lanes import MG_ESC_SYMBOLIC, MG_ESCAPE, MG_FORK
+from mythril_amd.laser import BreadthFirstSearchStrategy, LaserEVM
 from mythril_amd.laser import symbolic as sym
-from mythril_amd.laser.transaction import ACTORS
-from mythril_amd.smt.exponent_manager import exponent_function_manager
-from mythril_amd.smt.expr import Or, symbol_factory
 
 pytestmark = pytest.mark.gpu
 
@@ -37,18 +31,7 @@ def dev():
     d.close()
 
 
-def _initial(ws, addr, txid="50"):
-    sender = symbol_factory.BitVecSym(f"sender_{txid}", 256)
-    tx = MessageCallTransaction(world_state=ws, identifier=txid,
-                                gas_price=symbol_factory.BitVecSym(f"gas_price{txid}", 256),
-                                gas_limit=8_000_000, origin=sender, caller=sender,
-                                callee_account=ws[addr], call_data=SymbolicCalldata(txid),
-                                call_value=symbol_factory.BitVecSym(f"call_value{txid}", 256))
-    gs = tx.initial_global_state()
-    gs.transaction_stack.append((tx, None))
-    gs.world_state.constraints.append(
-        Or(*[tx.caller == symbol_factory.BitVecVal(a, 256) for a in ACTORS.values()]))
-    return gs
+_initial = symcosim.initial      # tests/test_gpu_transfers.py starts its symbolic calls with it too
 
 
 def _min_forks(name: str) -> int:
@@ -69,57 +52,12 @@ def test_device_symbolic_lanes_cosimulate_with_the_restatement(dev, name):
     while queue:
         batch_states = queue[:256]
         queue = queue[256:]
-        shape = vm._shape(batch_states)
-        b = LaneBatch(shape)
-        for i, s in enumerate(batch_states):
-            vm._pack(b, i, s)
-            b.steps[i] = 0
-        dev.alloc(shape)
-        dev.upload(b)
-        dev.step()
-        dev.download(b)
-        for i, s0 in enumerate(batch_states):
-            n = int(b.steps[i])
-            device_steps += n
-            st = int(b.status[i])
-            got = vm._materialise(b, i, copy(s0))
-            # the path constraints LaserEVM's record replay appends (EXP: the
-            # exponent manager's condition, instructions.py:624-638), in order
-            for r in b.records(i):
-                if r[1] == "symexp":
-                    _, cond = exponent_function_manager.create_condition(*sym.exp_operands(b, i, got, r[2]))
-                    got.world_state.constraints.append(cond)
-                elif r[1] == "exp":
-                    _, cond = exponent_function_manager.create_condition(
-                        symbol_factory.BitVecVal(r[2], 256), symbol_factory.BitVecVal(r[3], 256))
-                    got.world_state.constraints.append(cond)
-                elif r[1] == "symlen":          # sha3_ of a symbolic length (:1023-1028)
-                    got.world_state.constraints.append(sym.decode_node(b, i, got, r[2]) == r[3])
-            # the restatement: the same state, the same number of instructions (a
-            # halt or VmException counts as a step but leaves the state at its start)
-            ref = s0
-            for _ in range(n - (1 if st in (1, 2, 3, 5, 6) else 0)):
-                out = eng.step(ref)
-                assert len(out) == 1, (name, "the restatement forked or ended inside a device run")
-                ref = out[0]
-            assert got.mstate.pc == ref.mstate.pc
-            assert [x.raw for x in got.mstate.stack] == [x.raw for x in ref.mstate.stack], (name, got.mstate.pc)
-            assert [type(x) for x in got.mstate.stack] == [type(x) for x in ref.mstate.stack]
-            assert (got.mstate.min_gas_used, got.mstate.max_gas_used, got.mstate.depth) == \
-                (ref.mstate.min_gas_used, ref.mstate.max_gas_used, ref.mstate.depth)
-            assert got.mstate.memory.raw() == ref.mstate.memory.raw()
-            assert {p: e.raw for p, e in got.mstate.memory.symbolic_bytes().items()} == \
-                {p: e.raw for p, e in ref.mstate.memory.symbolic_bytes().items()}
-            # bytes at symbolic keys (MG_SYM_MSTOREK events), values and write order
-            assert [(k, v if isinstance(v, int) else v.raw)
-                    for k, v in got.mstate.memory.symbolic_key_bytes().items()] == \
-                [(k, v if isinstance(v, int) else v.raw) for k, v in ref.mstate.memory.symbolic_key_bytes().items()]
-            gst, rst = got.environment.active_account.storage, ref.environment.active_account.storage
-            if rst.is_chain:
-                assert [(k.raw, v.raw) for k, v in gst.chain()] == [(k.raw, v.raw) for k, v in rst.chain()]
-            else:
-                assert gst.slots() == rst.slots()
-            recs = b.records(i)
+        # per lane: pack, upload, step, download, decode, replay the records, step
+        # the restatement as far, compare everything (tests/symcosim.py)
+        lanes, _ = symcosim.cosimulate(dev, batch_states, vm=vm, eng=eng, name=name)
+        for ln in lanes:
+            device_steps += ln.steps
+            st, got, ref, recs = ln.status, ln.state, ln.ref, ln.records
             sym_sha3 += sum(1 for r in recs if r[1] == "symkeccak")
             sym_exp += sum(1 for r in recs if r[1] == "symexp")
             if st in (1, 2, 3) and any(r[1] == "symkeccak" for r in recs):
@@ -133,7 +71,7 @@ def test_device_symbolic_lanes_cosimulate_with_the_restatement(dev, name):
                     [(t.mstate.pc, tuple(c.raw for c in t.world_state.constraints)) for t in theirs]
                 queue.extend(t for t in mine if sym.lane_eligible(t))
             elif st == MG_ESCAPE:
-                assert (int(b.aux[i]) >> 8) in (MG_ESC_SYMBOLIC, 1, 2, 3, 4, 8)
+                assert ln.reason in (MG_ESC_SYMBOLIC, 1, 2, 3, 4, 8)
                 if name == "memjump":
                     # the host takes the jump (as LaserEVM's escape handler would):
                     # the paths past it come back to the device
