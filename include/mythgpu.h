@@ -62,7 +62,7 @@ extern "C" {
                               15: function-entry tracking (mg_lane_soa.fent,
                                   mg_code_fentries): the last JUMP / JUMPI landing
                                   on a dispatcher entry, for active_function_name;
-                                  additive: mg_eval_terms, mg_eval_min */
+                                  additive: mg_eval_terms, mg_eval_min, mg_lanes_fork */
 
 /* ------------------------------------------------------------------ errors */
 #define MG_OK          0
@@ -514,6 +514,66 @@ int         mg_lanes_upload_live(mg_ctx *ctx, const mg_lane_soa *host, uint32_t 
 /* Re-initialise every lane from the resident initial image on the device
  * (no host traffic): pc, sp, msize, gas, status, storage, steps.            */
 int         mg_lanes_reset(mg_ctx *ctx);
+
+/* The fork of a JUMPI on a symbolic condition (jumpi_, instructions.py:1558-1636:
+ * two copies of the state, one per branch, each with one more path constraint)
+ * as a lane-image operation on the device: nothing crosses PCIe but the index
+ * arrays below and the two result arrays.
+ *
+ * Fork i makes up to two successors of lane src[i]: the fall-through in lane
+ * dst_fall[i] and the jump in lane dst_jump[i].  A source is forkable when its
+ * status is MG_FORK, its flags have MG_LANE_SYMBOLIC and not MG_LANE_TAINT,
+ * sp >= 2, stag[sp-1] == 0 (a concrete target), stag[sp-2] != 0 (a symbolic
+ * condition) and its pc is an instruction of its code; otherwise made[i] =
+ * MG_FORK_BAD_SRC, cond[i] = 0 and no lane is written (a normal answer: the host
+ * does not know device statuses without a download).
+ *
+ * cond[i] = the source's stag[sp-2], 1 + the arena node of the condition.  Both
+ * successors keep that node at the same index of their copied arena; the host
+ * appends `condition` to the jump's constraints and Not(condition) to the
+ * fall-through's, as jumpi_ does.
+ *
+ * A successor is what the stepper's concrete JUMPI leaves when that side is
+ * taken: sp - 2, depth + 1, gas_min / gas_max + 10 (by hand, no out-of-gas
+ * check), steps + 1, status MG_RUNNING, aux 0, MG_LANE_HOOK_ACK cleared and the
+ * other flags kept.  Fall-through: pc + 1, and fent = pc + 1 when bit 1 of the
+ * JUMPI's function-entry flags is set.  Jump: idx = the ">="-resolve of the target when
+ * it fits 32 bits and is below the table's size; valid when the instruction at
+ * idx is a JUMPDEST; then pc = idx, and fent = idx when bit 0 of idx's flags is
+ * set.  An invalid target makes no jump lane (dst_jump[i] is untouched and
+ * MG_FORK_MADE_JUMP stays clear; the reference returns only the fall-through).
+ * Everything else is the source's, copied below its live bounds only: stack rows
+ * and stag below sp - 2, memory and mtag below msize, storage entries and sttag
+ * below storage_count, arena nodes below n_nodes, constants below n_consts,
+ * records below rec_len, trace below trace_len (the JUMPI is already in it),
+ * calldata and the environment words whole, and every remaining scalar (the
+ * Keccak / EXP event counts included).  Destination rows above those bounds and
+ * every lane not named keep their contents, as after an upload.  With coverage
+ * on, the JUMPI's byte is set when a successor is made.  The resident reset
+ * image is not touched: mg_lanes_reset and mg_run_batches still restart from
+ * the last upload.
+ *
+ * Checked on the host before any launch (MG_ESTATE: no batch, no upload or no
+ * symbolic planes; else MG_EINVAL; the message names the offending index; the
+ * device image is unchanged): every lane index is below n_lanes, all src are
+ * distinct, all destinations other than MG_FORK_NONE are distinct from one
+ * another and from every src except dst_fall[i] == src[i] (the source becomes
+ * its own fall-through in place), dst_jump[i] != src[i], made and cond are
+ * non-NULL when n > 0.  n == 0 succeeds and does nothing.  The number of
+ * launches and copies does not depend on n.                                   */
+#define MG_FORK_NONE      0xffffffffu  /* dst: do not make this successor          */
+#define MG_FORK_MADE_FALL 1u           /* made[]: the fall-through lane was written */
+#define MG_FORK_MADE_JUMP 2u           /* made[]: the jump lane was written         */
+#define MG_FORK_BAD_SRC   0x80000000u  /* made[]: src is not a forkable lane; nothing written */
+typedef struct mg_fork_batch {
+    uint32_t n, _pad;
+    const uint32_t *src;       /* [n] lanes stopped with MG_FORK                      */
+    const uint32_t *dst_fall;  /* [n] lane for the fall-through successor, MG_FORK_NONE,
+                                      or src[i] itself (the parent becomes it in place) */
+    const uint32_t *dst_jump;  /* [n] lane for the jump successor, or MG_FORK_NONE     */
+} mg_fork_batch;
+int         mg_lanes_fork(mg_ctx *ctx, const mg_fork_batch *forks,
+                          uint32_t *made /* [n] */, uint32_t *cond /* [n] */, float *kernel_ms);
 
 /* Replaces the LaserEVM.exec() drain for device-eligible lanes (svm.py:293-337
  * + execute_state svm.py:369-491 + Instruction.evaluate instructions.py:235-267):

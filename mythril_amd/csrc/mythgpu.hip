@@ -19,6 +19,7 @@
 #include "bv_eval.cuh"
 #include "lane_step.cuh"
 #include "sym_step.cuh"
+#include "lane_fork.cuh"
 #include "cc.h"
 
 // ------------------------------------------------------------------ context
@@ -1182,6 +1183,99 @@ extern "C" int mg_lanes_reset(mg_ctx *ctx) {
         return set_err(ctx, MG_ESTATE, "mg_lanes_reset needs an uploaded image with empty stacks and memory");
     hipLaunchKernelGGL(k_reset, dim3(blocks_for(ctx->L.n)), dim3(256), 0, ctx->stream, ctx->L, reset_image(ctx));
     HIPX(ctx, hipGetLastError());
+    return MG_OK;
+}
+
+// ---- mg_lanes_fork (lane_fork.cuh) -------------------------------------------
+// One H2D copy (the three index arrays and the copy list, packed in the pinned
+// buffer), three launches, one D2H copy (made and cond).
+extern "C" int mg_lanes_fork(mg_ctx *ctx, const mg_fork_batch *forks, uint32_t *made, uint32_t *cond,
+                             float *kernel_ms) {
+    if (!ctx) return MG_EINVAL;
+    if (!forks) return set_err(ctx, MG_EINVAL, "mg_lanes_fork: null batch");
+    if (!ctx->have_lanes) return set_err(ctx, MG_ESTATE, "mg_lanes_fork before mg_lanes_alloc");
+    if (!ctx->uploaded) return set_err(ctx, MG_ESTATE, "mg_lanes_fork before mg_lanes_upload");
+    if (!ctx->S.node) return set_err(ctx, MG_ESTATE, "mg_lanes_fork needs symbolic planes (mg_sym_alloc)");
+    if (kernel_ms) *kernel_ms = 0.f;
+    const uint32_t n = forks->n, n_lanes = ctx->L.n;
+    if (n == 0u) return MG_OK;
+    if (!forks->src || !forks->dst_fall || !forks->dst_jump || !made || !cond)
+        return set_err(ctx, MG_EINVAL, "mg_lanes_fork: src, dst_fall, dst_jump, made and cond are required");
+    if (n > n_lanes) return set_err(ctx, MG_EINVAL, "mg_lanes_fork: %u forks in a batch of %u lanes", n, n_lanes);
+    // every lane is named at most once: 1 = a source, 2 = a destination
+    std::vector<uint8_t> role(n_lanes, 0);
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t s = forks->src[i];
+        if (s >= n_lanes) return set_err(ctx, MG_EINVAL, "mg_lanes_fork: src[%u] = %u outside batch of %u", i, s, n_lanes);
+        if (role[s]) return set_err(ctx, MG_EINVAL, "mg_lanes_fork: src[%u] = %u is a source twice", i, s);
+        role[s] = 1;
+    }
+    // one copy per successor that lives in another lane than its source
+    std::vector<std::pair<uint32_t, uint32_t>> copies;   // (destination lane, fork | FORK_COPY_JUMP)
+    copies.reserve((size_t)n * 2u);
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t s = forks->src[i], df = forks->dst_fall[i], dj = forks->dst_jump[i];
+        if (df != MG_FORK_NONE && df != s) {
+            if (df >= n_lanes)
+                return set_err(ctx, MG_EINVAL, "mg_lanes_fork: dst_fall[%u] = %u outside batch of %u", i, df, n_lanes);
+            if (role[df])
+                return set_err(ctx, MG_EINVAL, "mg_lanes_fork: dst_fall[%u] = %u is already a %s", i, df,
+                               role[df] == 1 ? "source" : "destination");
+            role[df] = 2;
+            copies.emplace_back(df, i);
+        }
+        if (dj != MG_FORK_NONE) {
+            if (dj >= n_lanes)
+                return set_err(ctx, MG_EINVAL, "mg_lanes_fork: dst_jump[%u] = %u outside batch of %u", i, dj, n_lanes);
+            if (dj == s) return set_err(ctx, MG_EINVAL, "mg_lanes_fork: dst_jump[%u] = %u is its own source", i, dj);
+            if (role[dj])
+                return set_err(ctx, MG_EINVAL, "mg_lanes_fork: dst_jump[%u] = %u is already a %s", i, dj,
+                               role[dj] == 1 ? "source" : "destination");
+            role[dj] = 2;
+            copies.emplace_back(dj, i | FORK_COPY_JUMP);
+        }
+    }
+    std::sort(copies.begin(), copies.end());
+    const uint32_t nc = (uint32_t)copies.size();
+    HIPX(ctx, hipSetDevice(ctx->device));
+    // stage, in uint32 words: src, dst_fall, dst_jump [n each], copy_fork, copy_dst
+    // [nc each] go up; made, cond [n each] come back; jidx [n] stays on the device
+    const size_t up_words = (size_t)3u * n + (size_t)2u * nc, words = up_words + (size_t)3u * n;
+    int rc;
+    if ((rc = ensure_stage(ctx, words * 4u)) || (rc = ensure_hxfer(ctx, words * 4u))) return rc;
+    uint32_t *h = (uint32_t *)ctx->h_xfer, *d = (uint32_t *)ctx->d_stage;
+    std::memcpy(h, forks->src, (size_t)n * 4u);
+    std::memcpy(h + n, forks->dst_fall, (size_t)n * 4u);
+    std::memcpy(h + 2u * (size_t)n, forks->dst_jump, (size_t)n * 4u);
+    for (uint32_t c = 0; c < nc; ++c) {
+        h[3u * (size_t)n + c] = copies[c].second;
+        h[3u * (size_t)n + nc + c] = copies[c].first;
+    }
+    HIPX(ctx, hipMemcpyAsync(d, h, up_words * 4u, hipMemcpyHostToDevice, ctx->stream));
+    ForkArgs F{};
+    F.n = n; F.n_copies = nc; F.n_codes = (uint32_t)ctx->codes.size(); F.cov_on = ctx->cfg.coverage ? 1u : 0u;
+    F.src = d; F.dst_fall = d + n; F.dst_jump = d + 2u * (size_t)n;
+    F.copy_fork = d + 3u * (size_t)n; F.copy_dst = F.copy_fork + nc;
+    F.made = d + up_words; F.cond = F.made + n; F.jidx = F.cond + n;
+    if (kernel_ms) HIPX(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    hipLaunchKernelGGL(k_fork_check, dim3(blocks_for(n)), dim3(256), 0, ctx->stream, ctx->L, ctx->S, ctx->d_codes,
+                       ctx->d_a8, ctx->d_a32, F);
+    if (nc) {
+        // enough row workers to fill the chip when the copies are few (about 4096
+        // waves in all), four per copy tile when they are many
+        const uint32_t tiles = (nc + 63u) / 64u;
+        const uint32_t gy = std::min<uint32_t>(std::max<uint32_t>(1024u / tiles, 1u), 64u);
+        hipLaunchKernelGGL(k_fork_copy, dim3(tiles, gy), dim3(64, 4), 0, ctx->stream, ctx->L, ctx->S, F);
+    }
+    hipLaunchKernelGGL(k_fork_commit, dim3(blocks_for(n)), dim3(256), 0, ctx->stream, ctx->L, ctx->S, ctx->d_codes,
+                       ctx->d_a8, ctx->d_cov, F);
+    HIPX(ctx, hipGetLastError());
+    if (kernel_ms) HIPX(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+    HIPX(ctx, hipMemcpyAsync(h, F.made, (size_t)2u * n * 4u, hipMemcpyDeviceToHost, ctx->stream));
+    HIPX(ctx, hipStreamSynchronize(ctx->stream));
+    std::memcpy(made, h, (size_t)n * 4u);
+    std::memcpy(cond, h + n, (size_t)n * 4u);
+    if (kernel_ms) HIPX(ctx, hipEventElapsedTime(kernel_ms, ctx->ev0, ctx->ev1));
     return MG_OK;
 }
 

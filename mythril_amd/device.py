@@ -177,6 +177,24 @@ class GpuDevice:
     def reset(self):
         self._check(self.lib.mg_lanes_reset(self.ctx), "mg_lanes_reset")
 
+    def fork(self, src, dst_fall, dst_jump):
+        """mg_lanes_fork: make the JUMPI successors of the lanes `src` (stopped with
+        MG_FORK) in the lanes `dst_fall` / `dst_jump` on the device (MG_FORK_NONE:
+        not this one; dst_fall[i] == src[i]: in place).  uint32 arrays in;
+        returns (made uint32[n] of MG_FORK_MADE_* / MG_FORK_BAD_SRC, cond uint32[n] =
+        1 + the condition's arena node, kernel_ms)."""
+        arrs = [np.ascontiguousarray(np.asarray(a, dtype=np.uint32).reshape(-1)) for a in (src, dst_fall, dst_jump)]
+        n = arrs[0].size
+        if arrs[1].size != n or arrs[2].size != n:
+            raise ValueError("fork: src, dst_fall and dst_jump must have one entry per fork")
+        made = np.zeros(n, dtype=np.uint32)
+        cond = np.zeros(n, dtype=np.uint32)
+        batch = native.MgForkBatch(n, 0, arrs[0].ctypes.data, arrs[1].ctypes.data, arrs[2].ctypes.data)
+        ms = ctypes.c_float()
+        self._check(self.lib.mg_lanes_fork(self.ctx, ctypes.byref(batch), made.ctypes.data, cond.ctypes.data,
+                                           ctypes.byref(ms)), "mg_lanes_fork")
+        return made, cond, ms.value
+
     def step(self, hook_mask=None, max_steps: int = 1 << 30, max_depth: int = 0,
              horizon: int = 0) -> StepStats:
         """mg_step (horizon 0) or mg_step_until: lanes also pause once their

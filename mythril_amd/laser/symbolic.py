@@ -803,6 +803,22 @@ def jumpi_successors(state) -> list:
     return out
 
 
+def fork_conditions(b, i: int, state, cond_tag: int):
+    """The (negated, condi) pair jumpi_successors builds, for a fork the device
+    made (mg_lanes_fork): `cond_tag` is its cond[] answer, 1 + the arena node of
+    the JUMPI's condition in lane i of `b` -- the parent or either successor,
+    which keep the node at the same index.  Only that node is decoded.  The
+    fall-through gains `negated` and the jump `condi`, under jumpi_successors'
+    rules (a successor whose condition is_false does not exist; a condition whose
+    value is True is not appended)."""
+    if cond_tag <= 0:
+        raise ValueError("fork_conditions: not a symbolic condition (cond tag 0)")
+    condition = decode_node(b, i, state, int(cond_tag) - 1)
+    negated = Not(condition) if isinstance(condition, Bool) else condition == 0
+    condi = condition if isinstance(condition, Bool) else condition != 0
+    return negated, condi
+
+
 def _fork_copy(state):
     """deepcopy(global_state) of the reference's fork (world state, machine
     state and account copies; expressions are immutable and shared)."""

@@ -109,6 +109,11 @@ class MgMinBatch(ctypes.Structure):
                 ("obj_off", ctypes.c_void_p), ("obj_dag", ctypes.c_void_p)]
 
 
+class MgForkBatch(ctypes.Structure):
+    _fields_ = [("n", ctypes.c_uint32), ("_pad", ctypes.c_uint32), ("src", ctypes.c_void_p),
+                ("dst_fall", ctypes.c_void_p), ("dst_jump", ctypes.c_void_p)]
+
+
 # every symbol include/mythgpu.h declares: name -> (restype, argtypes)
 _P, _U32, _U64, _I = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int
 _PU32 = ctypes.POINTER(ctypes.c_uint32)
@@ -133,6 +138,7 @@ SIGNATURES = {
     "mg_lanes_download_live": (_I, [_P, _P, _U32, _U32]),
     "mg_lanes_upload_live": (_I, [_P, _P, _U32, _U32]),
     "mg_lanes_reset": (_I, [_P]),
+    "mg_lanes_fork": (_I, [_P, ctypes.POINTER(MgForkBatch), _P, _P, ctypes.POINTER(ctypes.c_float)]),
     "mg_step": (_I, [_P, _P, _U32, _U32, ctypes.POINTER(MgStepStats)]),
     "mg_step_async": (_I, [_P, _P, _U32, _U32]),
     "mg_run_batches": (_I, [_P, _P, _U32, _U32, _U32, ctypes.POINTER(MgStepStats)]),
