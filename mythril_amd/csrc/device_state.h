@@ -98,3 +98,22 @@ struct DevCounters {
 };
 
 #define MG_JRES_NONE 0xffffffffu
+
+// Kernel 1's Keccak result table: one per context, the second level behind the
+// per-wave LDS cache.  Direct-mapped, KT_SLOTS entries of KT_ENTRY dwords (128
+// bytes): 16 input dwords, 8 hash limbs, the state word at KT_STATE, padding.
+// It takes only SHA3 inputs of 64 aligned bytes that are one value in every lane
+// of a wave running the SHA3 (keccak(actor . slot): constants of an analysis that
+// every wave of every launch hashes again); the kernel fills it and it outlives
+// launches.  State: 0 = free, KT_BUSY = claimed (and left so if the claimant never
+// finished), otherwise the epoch of the launch that published the entry.  A launch
+// uses an entry only when 0 < state < its own epoch, i.e. one that a whole earlier
+// launch on the context's stream wrote: the kernel boundary orders those writes,
+// so the path needs no fences, and a stale state word can only read as free or as
+// the running launch's epoch, both a miss.  Insert-only: nothing is overwritten.
+#define KT_SLOTS 64u
+#define KT_ENTRY 32u
+#define KT_STATE 24u
+#define KT_BUSY 0xffffffffu
+#define KT_BYTES (KT_SLOTS * KT_ENTRY * 4u)
+#define KT_EPOCH_MAX 0xfffffff0u    // launch_step clears the table and restarts the epochs here

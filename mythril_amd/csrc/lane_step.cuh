@@ -380,7 +380,17 @@ struct StepEnv {
     uint32_t sn;         // s_pd holds instructions [0, sn) (the END sentinel included when staged whole)
     uint32_t tosmem;     // the caller keeps the stack's top two words in memory too (k_sym_step):
                          // no spill of T1 below a push
+    uint32_t *ktab;      // the context's Keccak table (device_state.h KT_*), or null: off / k_sym_step
+    uint32_t kepoch;     // this launch's epoch
 };
+
+// dword offset of the Keccak table entry (device_state.h KT_*) an input maps to
+DEV uint32_t ktab_slot(const uint32_t (&u)[16]) {
+    uint32_t h = 0u;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) h = (h ^ u[k]) * 0x9e3779b1u;
+    return (h >> 26) * KT_ENTRY;      // top 6 bits: KT_SLOTS = 64
+}
 
 // Executes the instruction decoded as (uk, ux) for one lane, exactly as the
 // reference would (three phases: checks, accumulate_gas, writes).  The fast
@@ -542,7 +552,38 @@ __device__ __forceinline__ void slow_step(LaneRegs &R, const StepEnv &E, uint32_
                     }
                 }
                 const uint64_t act = __ballot(true);
-                if (__ballot(hit) == act) {
+                const bool all_hit = __ballot(hit) == act;
+                // Second level, on a miss: the context's table (device_state.h KT_*), for an
+                // input that is one value in every lane of this dispatch.
+                uint32_t *kt = nullptr;           // the input's table entry when it is wave-uniform
+                uint32_t kt_state = KT_BUSY;
+                bool tab_hit = false;
+                if (!all_hit && E.ktab != nullptr && __ballot(cacheable) == act) {
+                    uint32_t u[16];
+                    bool uni = true;
+#pragma unroll
+                    for (int k = 0; k < 16; ++k) {
+                        u[k] = __builtin_amdgcn_readfirstlane(din[k]);
+                        uni = uni && din[k] == u[k];
+                    }
+                    if (__ballot(uni) == act) {
+                        kt = E.ktab + ktab_slot(u);
+                        // agent-scope loads: vector loads served by L2, never the scalar cache
+#define KT_LOAD(p_) __hip_atomic_load((p_), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+                        // the whole entry in one round trip (the loads are independent);
+                        // res is overwritten below unless the entry is taken
+                        kt_state = KT_LOAD(kt + KT_STATE);
+                        uint32_t diff = 0u;
+#pragma unroll
+                        for (int k = 0; k < 16; ++k) diff |= KT_LOAD(kt + k) ^ u[k];
+#pragma unroll
+                        for (int k = 0; k < 8; ++k) res.w[k] = KT_LOAD(kt + 16 + k);
+                        // usable: published by an earlier launch, and this input's
+                        tab_hit = kt_state != 0u && kt_state < E.kepoch && diff == 0u;
+#undef KT_LOAD
+                    }
+                }
+                if (all_hit || tab_hit) {
                     if (L.rec_cap) {
                         uint32_t *rp = L.rec + lane + (size_t)(rec_at + MG_REC_HEADER) * L.N;
 #pragma unroll
@@ -552,6 +593,8 @@ __device__ __forceinline__ void slow_step(LaneRegs &R, const StepEnv &E, uint32_
                     res = keccak_mem(V, a.w[0], b.w[0],
                                      L.rec_cap ? L.rec + lane + (size_t)(rec_at + MG_REC_HEADER) * L.N : nullptr,
                                      L.N);
+                }
+                if (!all_hit) {
                     const uint64_t ins = __ballot(cacheable && !hit);
                     if (ins != 0ull && (uint32_t)__builtin_ctzll(ins) == (threadIdx.x & 63u)) {
                         const uint32_t e = kc[KC_E * 24u + 1u] % KC_E;
@@ -563,6 +606,20 @@ __device__ __forceinline__ void slow_step(LaneRegs &R, const StepEnv &E, uint32_
                         kc[KC_E * 24u + 1u] = e + 1u;
                     }
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                    // a uniform input hashed here whose table slot read as free: the
+                    // first active lane claims the slot and, if it wins, publishes
+                    // the pair for later launches
+                    if (kt != nullptr && kt_state == 0u && (uint32_t)__builtin_ctzll(act) == (threadIdx.x & 63u)) {
+                        uint32_t expect = 0u;
+                        if (__hip_atomic_compare_exchange_strong(kt + KT_STATE, &expect, KT_BUSY, __ATOMIC_RELAXED,
+                                                                 __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
+#pragma unroll
+                            for (int k = 0; k < 16; ++k) kt[k] = din[k];
+#pragma unroll
+                            for (int k = 0; k < 8; ++k) kt[16 + k] = res.w[k];
+                            __hip_atomic_store(kt + KT_STATE, E.kepoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        }
+                    }
                 }
                 if (L.rec_cap) {
                     rec_head(L, lane, rec_at, MG_REC_KECCAK, b.w[0], L.steps[lane] + R.step, res);
@@ -866,6 +923,7 @@ __device__ uint32_t g_k1_clk[4096u * CLK_BINS];
                                  // the LDS-resident form)
 #define K1_PUSH_LDS 0x200u       // the push immediates are staged in LDS too (otherwise read from
                                  // the code arena at wave-uniform addresses)
+#define K1_NO_KTAB 0x400u        // the Keccak table is off (MG_K1_KTAB=0): every miss hashes
 #define K1_MW_SHIFT 16           // bits 16..23: LDS memory window per lane in 32-byte words
 #define K1_MW_MASK 0xffu
 
@@ -880,7 +938,9 @@ __global__ __launch_bounds__(LANE_BLOCK) void k_lane_step(DevLanes L, const DevC
                                                           unsigned long long *__restrict__ prof,
                                                           uint32_t win, uint32_t pd_cap, uint32_t jr_cap,
                                                           uint32_t horizon, uint32_t loop_bound,
-                                                          DevResetImage R, uint32_t lpw_flags) {
+                                                          DevResetImage R, uint32_t lpw_flags,
+                                                          uint32_t *ktab, uint32_t kepoch) {
+    // ktab: not const __restrict__, so that no load of it is moved to the scalar cache
     const uint32_t lpw = lpw_flags & K1_LPW_MASK;
     const bool lds_runs_on = (lpw_flags & K1_REG_RUNS) == 0u;
     const bool push_lds = (lpw_flags & K1_PUSH_LDS) != 0u;
@@ -1053,7 +1113,8 @@ __global__ __launch_bounds__(LANE_BLOCK) void k_lane_step(DevLanes L, const DevC
     const uint8_t *__restrict__ gops = a8 + C.op_off;
     const uint8_t *__restrict__ gfent = a8 + C.fent_off;
     const StepEnv E{&L, C, a8, a32, s_win, s_mw, s_pd, s_push, s_prof, s_kc + (threadIdx.x >> 6) * KC_WAVE,
-                    txlim, glim, lane, tid, lanes_pb, win, flags, sflag, psflag, prof ? 1u : 0u, mw, sn, 0u};
+                    txlim, glim, lane, tid, lanes_pb, win, flags, sflag, psflag, prof ? 1u : 0u, mw, sn, 0u,
+                    (lpw_flags & K1_NO_KTAB) ? nullptr : ktab, kepoch};
 
     // Decode the instruction at pc and run the checks svm.execute_state makes
     // before evaluating it (svm.py:369-402): depth cut-off, past-the-end pc,

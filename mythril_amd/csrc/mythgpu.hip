@@ -75,6 +75,10 @@ struct mg_ctx {
     size_t h_ctr_pin_cap = 0;
     std::vector<void *> retired_host;
     std::vector<hipEvent_t> ev_batch;
+    // kernel 1's Keccak result table (lane_step.cuh KT_*): per context, because a
+    // context's launches are ordered on its one stream; filled by the kernel
+    uint32_t *d_ktab = nullptr;
+    uint32_t k_epoch = 0;                // the last k_lane_step launch's epoch (the first is 1)
     // kernel 2
     BvState bv{};
 };
@@ -211,6 +215,8 @@ extern "C" int mg_open(int device, mg_ctx **out) {
         uint2 dec[256];
         build_decode(dec);
         if (hipMemcpyToSymbol(HIP_SYMBOL(kDec), dec, sizeof dec) != hipSuccess) { rc = MG_EDEVICE; break; }
+        if (hipMalloc((void **)&ctx->d_ktab, KT_BYTES) != hipSuccess) { rc = MG_ENOMEM; break; }
+        if (hipMemset(ctx->d_ktab, 0, KT_BYTES) != hipSuccess) { rc = MG_EDEVICE; break; }
         const char *lpw = getenv("MG_LANES_PER_WAVE");
         if (lpw && lpw[0]) {
             const long v = strtol(lpw, nullptr, 10);
@@ -243,6 +249,7 @@ extern "C" void mg_close(mg_ctx *ctx) {
     hipFree(ctx->d_stage);
     hipFree(ctx->d_tprog);
     hipFree(ctx->d_tforce);
+    hipFree(ctx->d_ktab);
     if (ctx->ev0) hipEventDestroy(ctx->ev0);
     if (ctx->ev1) hipEventDestroy(ctx->ev1);
     for (hipEvent_t e : ctx->ev_batch) hipEventDestroy(e);
@@ -1361,9 +1368,11 @@ static LdsPlan lds_plan(const mg_ctx *ctx) {
 // MG_K1_RUNS=reg: straight-line runs in the register form only (the fallback
 // form; forced for the parity tests and A/B runs,
 // read per launch so one process can alternate the two forms)
+// MG_K1_KTAB=0: the Keccak result table off (A/B runs; on by default)
 static uint32_t k1_flags() {
     const char *r = getenv("MG_K1_RUNS");
-    return (r && std::string(r) == "reg") ? K1_REG_RUNS : 0u;
+    const char *t = getenv("MG_K1_KTAB");
+    return ((r && std::string(r) == "reg") ? K1_REG_RUNS : 0u) | ((t && t[0] == '0' && !t[1]) ? K1_NO_KTAB : 0u);
 }
 
 // plan / kflags: a caller launching many batches computes the LDS plan and the
@@ -1394,13 +1403,21 @@ static int launch_step(mg_ctx *ctx, const uint64_t hook_mask[4], uint32_t max_st
     if (ctr && blocks_for(ctx->L.n, lane_block(ctx)) > ctx->ctr_cap)
         return set_err(ctx, MG_EINVAL, "launch of %u blocks exceeds the %u statistics slots",
                        blocks_for(ctx->L.n, lane_block(ctx)), ctx->ctr_cap);
+    // Keccak table epoch: this launch publishes under it and reads only older ones.
+    // Before the epochs run out the table is cleared behind the earlier launches
+    // on the stream and they start again.
+    if (ctx->k_epoch >= KT_EPOCH_MAX) {
+        HIPX(ctx, hipMemsetAsync(ctx->d_ktab, 0, KT_BYTES, ctx->stream));
+        ctx->k_epoch = 0;
+    }
+    ++ctx->k_epoch;
     hipLaunchKernelGGL(loop_bound ? k_lane_step<true> : k_lane_step<false>, dim3(blocks_for(ctx->L.n, lane_block(ctx))),
                        dim3(LANE_BLOCK), P.bytes, ctx->stream, ctx->L,
                        ctx->d_codes, ctx->d_a8, ctx->d_a32, ctx->d_cov, ctx->cfg.coverage ? 1u : 0u, m[0], m[1],
                        m[2], m[3], max_steps, max_depth, ctr, prof, P.win, P.pd_cap, P.jr_cap, horizon,
                        loop_bound, reset ? *reset : DevResetImage{},
                        ctx->lpw | (kflags >= 0 ? (uint32_t)kflags : k1_flags()) | (P.push_lds ? K1_PUSH_LDS : 0u) |
-                       (P.mw32 << K1_MW_SHIFT));
+                       (P.mw32 << K1_MW_SHIFT), ctx->d_ktab, ctx->k_epoch);
     HIPX(ctx, hipGetLastError());
     // symbolic and taint lanes: the concrete stepper left them untouched (counted as running)
     // (a profiling pass counts their opcodes into the same histogram)

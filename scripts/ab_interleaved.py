@@ -65,7 +65,8 @@ def k1(dev, variants, rounds, code_name="overflow.sol.o"):
                 os.environ.pop(kv.partition("=")[0], None)
     for v, ms in res.items():
         print(json.dumps({"kernel": "k_lane_step", "code": code_name, "variant": v, "min_ms": min(ms),
-                          "median_ms": statistics.median(ms),
+                          "median_ms": statistics.median(ms), "max_ms": max(ms),
+                          "rounds_ms": [round(x, 5) for x in ms],
                           "G_lane_steps_s": steps / min(ms) / 1e6}), flush=True)
 
 
