@@ -86,9 +86,9 @@ struct DevCode {
     uint32_t jres_off;   // u32 [n_jres]             first index with addr >= t
     uint32_t bytes_off;  // u8  [n_bytes]            full bytecode
     uint32_t cov_off;    // u8  [n_instr]            coverage bytes
-    uint32_t run_off;    // u32 [n_instr][2]         straight-line run from each instruction
+    uint32_t run_off[2]; // u32 [n_instr][2]         straight-line run from each instruction: [0] the run
+                         //                          set with the environment pushes, [1] without (MG_K1_RUNENV=0)
     uint32_t fent_off;   // u8  [n_instr]            bit 0: index is a function entry, bit 1: index + 1 is
-    uint32_t _pad;
 };
 
 // Per-launch statistics accumulated by the stepping kernel.

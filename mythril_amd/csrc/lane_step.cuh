@@ -29,6 +29,7 @@ struct OpInfo {
 #define MG_K1_PF 0
 #endif
 #define RUN_MAX 64u   // longest straight-line run executed as one block
+static_assert(RUN_MAX == runtab::RUN_LEN_MAX, "the run table is built for this length");
 static_assert(RUN_MAX <= 64u, "a run is read as one pre-decoded word per wave lane");
 #define BIG_END (1ull << 32)
 #define HUGE_GAS (1ull << 62)
@@ -905,6 +906,24 @@ __device__ __forceinline__ void reset_lane(const DevLanes &L, const DevResetImag
         }
 }
 
+// The lane constant an environment opcode of the run set pushes (run_table.h
+// env_push; `instr`: the opcode's instruction index, for PC).
+DEV U256 env_word(const LaneView &V, const DevCode &C, const uint32_t *a32, uint32_t op, uint32_t instr,
+                  uint32_t msize) {
+    switch (op) {
+    case 0x30: return V.env(0);                          // ADDRESS
+    case 0x32: return V.env(2);                          // ORIGIN
+    case 0x33: return V.env(1);                          // CALLER
+    case 0x34: return V.env(3);                          // CALLVALUE
+    case 0x3a: return V.env(4);                          // GASPRICE
+    case 0x36: return u_small(V.L.calldata_len[V.lane]);
+    case 0x38: return u_small(C.n_bytes);                // CODESIZE
+    case 0x45: return u_small(MG_MSTATE_GAS_LIMIT);
+    case 0x58: return u_small(a32[C.addr_off + instr]);
+    default: return u_small(msize);                      // MSIZE
+    }
+}
+
 #ifdef MG_K1_CLOCKS
 // Diagnostic build only (scripts/k1_clocks.py): shader-clock cycles per wave,
 // binned by the opcode each dispatch-loop iteration executed (bin 256: a
@@ -924,6 +943,7 @@ __device__ uint32_t g_k1_clk[4096u * CLK_BINS];
 #define K1_PUSH_LDS 0x200u       // the push immediates are staged in LDS too (otherwise read from
                                  // the code arena at wave-uniform addresses)
 #define K1_NO_KTAB 0x400u        // the Keccak table is off (MG_K1_KTAB=0): every miss hashes
+#define K1_NO_RUNENV 0x1000u     // the run table without the environment pushes (MG_K1_RUNENV=0)
 #define K1_MW_SHIFT 16           // bits 16..23: LDS memory window per lane in 32-byte words
 #define K1_MW_MASK 0xffu
 
@@ -1023,6 +1043,8 @@ __global__ __launch_bounds__(LANE_BLOCK) void k_lane_step(DevLanes L, const DevC
         const DevCode BC = codes[bcode];
         const uint32_t ns = min(BC.n_instr, pd_cap - 1u);   // staged prefix
         if (ns > 0u) {
+            // run table variant (selected, not indexed: a dynamic index would put BC in scratch)
+            const uint32_t run_off = (lpw_flags & K1_NO_RUNENV) ? BC.run_off[1] : BC.run_off[0];
             // pre-decode: opcode, gas, stack counts, kind, and the hook bit (bit 31)
             for (uint32_t i = threadIdx.x; i < ns; i += blockDim.x) {
                 const uint32_t op = a8[BC.op_off + i];
@@ -1031,7 +1053,7 @@ __global__ __launch_bounds__(LANE_BLOCK) void k_lane_step(DevLanes L, const DevC
                 const uint32_t hook = (uint32_t)((hm >> (op & 63u)) & 1ull);
                 s_pd[i] = make_uint4(d.x, op | (d.y << 8) | pd_flags(op, d.y, hook) |
                                               ((uint32_t)a8[BC.fent_off + i] << 22),
-                                     a32[BC.run_off + 2u * i], a32[BC.run_off + 2u * i + 1u]);
+                                     a32[run_off + 2u * i], a32[run_off + 2u * i + 1u]);
                 s_cov[i] = 0;
             }
             if (threadIdx.x == 0 && ns == BC.n_instr)
@@ -1211,9 +1233,12 @@ __global__ __launch_bounds__(LANE_BLOCK) void k_lane_step(DevLanes L, const DevC
                 asm volatile("" : "+s"(usp));
                 const bool lds_run = lds_runs_on && usp >= rneed && usp + rpeak <= win &&
                                      usp + rpeak <= stack_lim;
+                // a lane of a creation transaction leaves a run that holds CALLDATASIZE or
+                // CODESIZE to the single-instruction path, which escapes there
+                const bool cre = creation && (rx & runtab::RX_CRE) != 0u;
                 const bool in_run = live && pc == upc && sp >= rneed && sp + rpeak <= stack_lim &&
                                     gmin + rg0 < glim && executed + rlen <= lane_max &&
-                                    (!lds_run || sp == usp);
+                                    (!lds_run || sp == usp) && !cre;
                 // the run's pre-decoded words, one per wave lane (rlen <= RUN_MAX = 64),
                 // read by the whole wave in one LDS access; instruction k is then
                 // v_readlane(k) instead of a dependent LDS round trip per instruction
@@ -1246,6 +1271,10 @@ __global__ __launch_bounds__(LANE_BLOCK) void k_lane_step(DevLanes L, const DevC
                                 V.set_wstack(s - 1u - d, x);
                                 break;
                             }
+                            case K_ENV:
+                                V.set_wstack(s, env_word(V, C, a32, rop, upc + k, msize));
+                                ++s;
+                                break;
                             case K_POP:
                                 --s;
                                 break;
@@ -1327,6 +1356,12 @@ __global__ __launch_bounds__(LANE_BLOCK) void k_lane_step(DevLanes L, const DevC
                                     V.set_stack(sp - 1u - d, T0);
                                     T0 = x;
                                 }
+                                break;
+                            }
+                            case K_ENV: {
+                                const U256 v = env_word(V, C, a32, rop, upc + k, msize);
+                                if (sp >= 2u) V.set_stack(sp - 2u, T1);
+                                T1 = T0; T0 = v; ++sp;
                                 break;
                             }
                             case K_POP:

@@ -17,6 +17,7 @@
 #include <cstdlib>
 #include <new>
 #include "bv_eval.cuh"
+#include "run_table.h"
 #include "lane_step.cuh"
 #include "sym_step.cuh"
 #include "lane_fork.cuh"
@@ -394,47 +395,19 @@ extern "C" int mg_load_code(mg_ctx *ctx, const uint8_t *code, size_t n, uint32_t
     // depth it needs, the growth it peaks at and the table gas of its simple
     // part (jumps add their 8 / 10 by hand), so a lane can check once and
     // execute the run without per-instruction checks (lane_step.cuh).
-    // rx = len | need << 8 | peak << 16 | jump kind << 24 (1 JUMP, 2 JUMPI).
+    // rx = len | need << 8 | peak << 16 | jump kind << 24 (1 JUMP, 2 JUMPI) | RX_CRE
+    // (run_table.h).  Two variants: [0] with the environment pushes in the run
+    // set, [1] without (MG_K1_RUNENV=0 picks it per launch).
     {
         const size_t ni = ops.size();
-        std::vector<uint32_t> rx(ni + 1, 0u), ry(ni + 1, 0u);
-        std::vector<int> need(ni + 1, 0), peak(ni + 1, 0), len(ni + 1, 0), jk(ni + 1, 0);
-        std::vector<uint32_t> g0(ni + 1, 0u), g1(ni + 1, 0u);
-        for (size_t i = ni; i-- > 0;) {
-            const uint32_t b = ops[i];
-            int req = -1, d = 0;
-            if (b >= 0x60 && b <= 0x7f) { req = 0; d = 1; }
-            else if (b >= 0x80 && b <= 0x8f) { req = (int)(b - 0x7f); d = 1; }
-            else if (b >= 0x90 && b <= 0x9f) { req = (int)(b - 0x8e); d = 0; }
-            else if (b == 0x50) { req = 1; d = -1; }
-            else if (b == 0x5b) { req = 0; d = 0; }
-            else if (b == 0x15 || b == 0x19) { req = 1; d = 0; }
-            else if (b <= 0x03 && b >= 0x01) { req = 2; d = -1; }
-            else if (b == 0x0b || (b >= 0x10 && b <= 0x1d)) { req = 2; d = -1; }
-            if (b == 0x56 || b == 0x57) {               // a jump ends the run it closes
-                len[i] = 1;
-                need[i] = b == 0x56 ? 1 : 2;
-                peak[i] = 0;
-                jk[i] = b == 0x56 ? 1 : 2;
-                g0[i] = g1[i] = 0u;
-                rx[i] = 1u | ((uint32_t)need[i] << 8) | ((uint32_t)jk[i] << 24);
-                ry[i] = 0u;
-                continue;
-            }
-            if (req < 0) continue;                      // not simple: runs end here
-            const bool cont = len[i + 1] > 0 && len[i + 1] < RUN_MAX;
-            len[i] = 1 + (cont ? len[i + 1] : 0);
-            need[i] = std::max(req, (cont ? need[i + 1] : 0) - d);
-            peak[i] = std::max(0, d + (cont ? peak[i + 1] : 0));
-            jk[i] = cont ? jk[i + 1] : 0;
-            g0[i] = t[b].gmin + (cont ? g0[i + 1] : 0u);
-            g1[i] = t[b].gmax + (cont ? g1[i + 1] : 0u);
-            rx[i] = (uint32_t)len[i] | ((uint32_t)need[i] << 8) | ((uint32_t)peak[i] << 16) |
-                    ((uint32_t)jk[i] << 24);
-            ry[i] = g0[i] | (g1[i] << 16);
+        uint32_t gt0[256], gt1[256];
+        for (int b = 0; b < 256; ++b) { gt0[b] = t[b].gmin; gt1[b] = t[b].gmax; }
+        for (int v = 0; v < 2; ++v) {
+            std::vector<uint32_t> rx, ry;
+            runtab::run_table(ops.data(), ni, gt0, gt1, v == 0, rx, ry);
+            dc.run_off[v] = (uint32_t)ctx->a32.size();
+            for (size_t i = 0; i < ni; ++i) { ctx->a32.push_back(rx[i]); ctx->a32.push_back(ry[i]); }
         }
-        dc.run_off = (uint32_t)ctx->a32.size();
-        for (size_t i = 0; i < ni; ++i) { ctx->a32.push_back(rx[i]); ctx->a32.push_back(ry[i]); }
     }
     dc.cov_off = ctx->cov_total;
     ctx->cov_total += dc.n_instr + 1u;
@@ -1369,10 +1342,13 @@ static LdsPlan lds_plan(const mg_ctx *ctx) {
 // form; forced for the parity tests and A/B runs,
 // read per launch so one process can alternate the two forms)
 // MG_K1_KTAB=0: the Keccak result table off (A/B runs; on by default)
+// MG_K1_RUNENV=0: the run table without the environment pushes (A/B runs; on by default)
 static uint32_t k1_flags() {
     const char *r = getenv("MG_K1_RUNS");
     const char *t = getenv("MG_K1_KTAB");
-    return ((r && std::string(r) == "reg") ? K1_REG_RUNS : 0u) | ((t && t[0] == '0' && !t[1]) ? K1_NO_KTAB : 0u);
+    const char *e = getenv("MG_K1_RUNENV");
+    return ((r && std::string(r) == "reg") ? K1_REG_RUNS : 0u) | ((t && t[0] == '0' && !t[1]) ? K1_NO_KTAB : 0u) |
+           ((e && e[0] == '0' && !e[1]) ? K1_NO_RUNENV : 0u);
 }
 
 // plan / kflags: a caller launching many batches computes the LDS plan and the

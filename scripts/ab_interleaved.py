@@ -39,7 +39,8 @@ def k2(dev, variants, rounds, n_dags):
 
 
 def k1(dev, variants, rounds, code_name="overflow.sol.o"):
-    """variants: "VAR=value[,VAR2=value]" strings (env switches read per launch)."""
+    """variants: "VAR=value[,VAR2=value]" strings (env switches read per launch:
+    MG_K1_RUNS, MG_K1_KTAB, MG_K1_RUNENV)."""
     code = workloads.bytecode(code_name) if code_name.endswith(".o") else workloads.large_code()
     cid = dev.load_code(code)
     sels = None if code_name.endswith(".o") else workloads.dispatch_selectors(code)

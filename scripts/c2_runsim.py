@@ -17,7 +17,9 @@ RUN_MAX = 64
 
 
 def simple(b):
-    return (0x60 <= b <= 0x7F or 0x80 <= b <= 0x9F or b in (0x50, 0x5B, 0x15, 0x19)
+    # with the lane-constant pushes (ADDRESS ORIGIN CALLER CALLVALUE CALLDATASIZE CODESIZE
+    # GASPRICE GASLIMIT PC MSIZE); RETURNDATASIZE stays a single dispatch
+    return (b in (0x30, 0x32, 0x33, 0x34, 0x36, 0x38, 0x3A, 0x45, 0x58, 0x59) or 0x60 <= b <= 0x7F or 0x80 <= b <= 0x9F or b in (0x50, 0x5B, 0x15, 0x19)
             or 0x01 <= b <= 0x03 or b == 0x0B or 0x10 <= b <= 0x1D)
 
 
