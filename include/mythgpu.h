@@ -62,7 +62,8 @@ extern "C" {
                               15: function-entry tracking (mg_lane_soa.fent,
                                   mg_code_fentries): the last JUMP / JUMPI landing
                                   on a dispatcher entry, for active_function_name;
-                                  additive: mg_eval_terms, mg_eval_min, mg_lanes_fork */
+                                  additive: mg_eval_terms, mg_eval_min, mg_lanes_fork,
+                                  mg_explore_alloc / mg_explore / mg_explore_download */
 
 /* ------------------------------------------------------------------ errors */
 #define MG_OK          0
@@ -574,6 +575,79 @@ typedef struct mg_fork_batch {
 } mg_fork_batch;
 int         mg_lanes_fork(mg_ctx *ctx, const mg_fork_batch *forks,
                           uint32_t *made /* [n] */, uint32_t *cond /* [n] */, float *kernel_ms);
+
+/* The step-and-fork loop on the device (the drain of svm.py:293-337 with jumpi_,
+ * instructions.py:1558-1636, as its only fork): up to max_rounds rounds, each one
+ * stepping launch as mg_step makes it, then the fork of every lane that stopped at
+ * a symbolic JUMPI, planned where the statuses are.  The host reads one small
+ * counter block per round (one stream synchronisation) and uploads nothing after
+ * the free list; the numbers of launches and copies per round do not depend on the
+ * number of forks.
+ *
+ * mg_explore_alloc (after mg_sym_alloc, once per batch; freed with the lanes)
+ * adds three per-lane planes.  path: up to path_cap entries per lane, entry =
+ * cond_tag << 1 | side, where cond_tag is mg_lanes_fork's cond[] value (1 + the
+ * arena node of the JUMPI's condition, which every descendant keeps at that index
+ * of its copied arena) and side is 1 for the jump and 0 for the fall-through.
+ * path_len: the number of entries.  root: the lane's lineage.  mg_explore starts
+ * (on the device) by setting root[l] = l and path_len[l] = 0 for every lane, so a
+ * lane that comes back has root = the lane its ancestor held when the call began
+ * and path = the branches taken since, oldest first; the host appends `condition`
+ * for a side-1 entry and Not(condition) for a side-0 entry, as jumpi_ does.
+ *
+ * The plan of a round.  A lane is a source under mg_lanes_fork's test, unchanged
+ * (status MG_FORK, MG_LANE_SYMBOLIC and not MG_LANE_TAINT, 2 <= sp <= stack_cap, a
+ * concrete target, a symbolic condition, pc inside its code), and when it is not
+ * in the unused part of the free list.  Taint lanes and lanes with a symbolic
+ * target are no sources: they stay MG_FORK and are counted nowhere.  A source with
+ * path_len == path_cap is left untouched, still MG_FORK, and counts in path_full.
+ * The fall-through is always made in place (dst_fall == src).  A source whose
+ * target is no JUMPDEST forks in place only and takes no free lane (the reference
+ * returns only the fall-through).  The sources with a valid target are ranked in
+ * ascending lane order; number r of the round takes free_lanes[used + r] as its
+ * jump lane, `used` being the entries earlier rounds of this call took.  When the
+ * list runs short the lowest lanes win; the others are left wholly untouched, still
+ * MG_FORK, and count in starved: the host forks them by mg_lanes_fork.  n_free == 0
+ * is allowed (every fork with a valid target is starved).  The successors are
+ * exactly mg_lanes_fork's for (src, dst_fall = src, dst_jump = that free lane or
+ * MG_FORK_NONE): the same kernels make them, so coverage, the loop-bound trace,
+ * records and the resident reset image behave as stated there.  Then the jump
+ * child takes the source's root and path plus a side-1 entry, and the source gains
+ * the side-0 entry.
+ *
+ * Which lanes are free is the caller's statement: a free lane's contents are
+ * overwritten when it is handed out (below its source's live bounds, as in
+ * mg_lanes_fork), whatever its status was; it is stepped like any lane until then.
+ * Entries free_lanes[free_used ...] were not used.
+ *
+ * The loop ends after a round that planned no fork and found no lane MG_RUNNING,
+ * or after max_rounds rounds.  Lanes that forked in the last round are MG_RUNNING
+ * on return.  stats: rounds run; forks made; made_jump = jump lanes written =
+ * free lanes used in all (free_used); starved and path_full summed over the rounds
+ * (a lane left in place counts again each round); running = lanes MG_RUNNING on
+ * return; lane_steps and kernel_ms (first launch to last) over the whole call.
+ *
+ * Checked on the host before any launch (the device image is unchanged):
+ * MG_ESTATE without a batch, an upload, symbolic planes or explore planes;
+ * MG_EINVAL when max_rounds == 0 (the loop is bounded by its argument), when
+ * free_lanes is NULL with n_free > 0, or when free_lanes is not strictly ascending
+ * with every entry below n_lanes (the message names the index).
+ *
+ * mg_explore_download: lanes [first, first + n); path is lane-major on the host,
+ * [n][path_cap] (lane i's entries are path[i * path_cap ...]), entries at and
+ * above path_len[i] are 0.                                                      */
+int         mg_explore_alloc(mg_ctx *ctx, uint32_t path_cap);
+typedef struct mg_explore_stats {
+    uint32_t rounds, forks, made_jump, starved, path_full, free_used, running, _pad;
+    uint64_t lane_steps;
+    float    kernel_ms, _padf;
+} mg_explore_stats;
+int         mg_explore(mg_ctx *ctx, const uint64_t hook_mask[4], uint32_t max_steps,
+                       uint32_t max_depth, uint32_t max_rounds, const uint32_t *free_lanes,
+                       uint32_t n_free, mg_explore_stats *stats);
+int         mg_explore_download(mg_ctx *ctx, uint32_t *path /* [n][path_cap] */,
+                                uint32_t *path_len /* [n] */, uint32_t *root /* [n] */,
+                                uint32_t first, uint32_t n);
 
 /* Replaces the LaserEVM.exec() drain for device-eligible lanes (svm.py:293-337
  * + execute_state svm.py:369-491 + Instruction.evaluate instructions.py:235-267):

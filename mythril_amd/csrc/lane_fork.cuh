@@ -41,31 +41,42 @@ struct ForkArgs {
 #define FORK_COPY_JUMP 0x80000000u
 #define FORK_GAS 10u   // JUMPI's gas, added by hand as the stepper does (no out-of-gas check)
 
+// Forkability and jump resolution of lane s, the one predicate of mg_lanes_fork's
+// contract: k_fork_check and the explorer's plan (lane_explore.cuh) both call it, so
+// the two cannot drift.  False: s is not a forkable source.  True: cond = the
+// condition's tag; jidx = the jump's instruction index when the jump is wanted and
+// its target resolves to a JUMPDEST, else MG_JRES_NONE.
+DEV bool fork_probe(const DevLanes &L, const DevSym &S, const DevCode *__restrict__ codes,
+                    const uint8_t *__restrict__ a8, const uint32_t *__restrict__ a32, uint32_t n_codes, uint32_t s,
+                    bool want_jump, uint32_t &cond, uint32_t &jidx) {
+    const size_t N = L.N;
+    cond = 0u; jidx = MG_JRES_NONE;
+    const uint32_t flags = L.flags[s], sp = L.sp[s], cid = L.code_id[s], pc = L.pc[s];
+    if (!(L.status[s] == MG_FORK && (flags & MG_LANE_SYMBOLIC) && !(flags & MG_LANE_TAINT) && sp >= 2u &&
+          sp <= L.stack_cap && cid < n_codes && pc < codes[cid].n_instr))
+        return false;
+    const DevCode C = codes[cid];
+    const uint32_t t_target = S.stag[(size_t)(sp - 1u) * N + s], t_cond = S.stag[(size_t)(sp - 2u) * N + s];
+    if (!(t_target == 0u && t_cond != 0u)) return false;
+    cond = t_cond;
+    if (want_jump) {
+        const U256 a = ld_word(gv(L.stack), (size_t)(sp - 1u) * N + s);
+        if (u_fits32(a) && a.w[0] < C.n_jres) {
+            const uint32_t idx = a32[C.jres_off + a.w[0]];
+            if (idx < C.n_instr && a8[C.op_off + idx] == 0x5bu) jidx = idx;
+        }
+    }
+    return true;
+}
+
 __global__ __launch_bounds__(256) void k_fork_check(DevLanes L, DevSym S, const DevCode *__restrict__ codes,
                                                     const uint8_t *__restrict__ a8,
                                                     const uint32_t *__restrict__ a32, ForkArgs F) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= F.n) return;
-    const uint32_t s = F.src[i];
-    const size_t N = L.N;
-    uint32_t made = MG_FORK_BAD_SRC, cond = 0u, jidx = MG_JRES_NONE;
-    const uint32_t flags = L.flags[s], sp = L.sp[s], cid = L.code_id[s], pc = L.pc[s];
-    if (L.status[s] == MG_FORK && (flags & MG_LANE_SYMBOLIC) && !(flags & MG_LANE_TAINT) && sp >= 2u &&
-        sp <= L.stack_cap && cid < F.n_codes && pc < codes[cid].n_instr) {
-        const DevCode C = codes[cid];
-        const uint32_t t_target = S.stag[(size_t)(sp - 1u) * N + s], t_cond = S.stag[(size_t)(sp - 2u) * N + s];
-        if (t_target == 0u && t_cond != 0u) {
-            made = F.dst_fall[i] != MG_FORK_NONE ? MG_FORK_MADE_FALL : 0u;
-            cond = t_cond;
-            if (F.dst_jump[i] != MG_FORK_NONE) {
-                const U256 a = ld_word(gv(L.stack), (size_t)(sp - 1u) * N + s);
-                if (u_fits32(a) && a.w[0] < C.n_jres) {
-                    const uint32_t idx = a32[C.jres_off + a.w[0]];
-                    if (idx < C.n_instr && a8[C.op_off + idx] == 0x5bu) { made |= MG_FORK_MADE_JUMP; jidx = idx; }
-                }
-            }
-        }
-    }
+    uint32_t made = MG_FORK_BAD_SRC, cond, jidx;
+    if (fork_probe(L, S, codes, a8, a32, F.n_codes, F.src[i], F.dst_jump[i] != MG_FORK_NONE, cond, jidx))
+        made = (F.dst_fall[i] != MG_FORK_NONE ? MG_FORK_MADE_FALL : 0u) | (jidx != MG_JRES_NONE ? MG_FORK_MADE_JUMP : 0u);
     F.made[i] = made; F.cond[i] = cond; F.jidx[i] = jidx;
 }
 

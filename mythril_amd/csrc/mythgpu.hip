@@ -21,6 +21,7 @@
 #include "lane_step.cuh"
 #include "sym_step.cuh"
 #include "lane_fork.cuh"
+#include "lane_explore.cuh"
 #include "cc.h"
 
 // ------------------------------------------------------------------ context
@@ -48,6 +49,9 @@ struct mg_ctx {
     DevLanes L{};
     DevSym S{};                          // symbolic planes (mg_sym_alloc), freed with the lanes
     DevTaint T{};                        // taint planes (mg_taint_alloc), freed with the lanes
+    DevExplore E{};                      // path planes and plan scratch (mg_explore_alloc), freed with the lanes
+    ExploreCtr *d_ectr = nullptr;        // the round's counter block (with E)
+    ExploreCtr *h_ectr = nullptr;        // its pinned host side (freed by mg_close)
     uint32_t *d_tprog = nullptr;         // [256] taint action words (mg_taint_program)
     uint8_t *d_tforce = nullptr;         // per code instruction (coverage layout): host-run hooks
     size_t cap_tforce = 0;
@@ -237,6 +241,8 @@ static void free_lanes(mg_ctx *ctx) {
     ctx->L = DevLanes{};
     ctx->S = DevSym{};
     ctx->T = DevTaint{};
+    ctx->E = DevExplore{};
+    ctx->d_ectr = nullptr;
     ctx->d_ctr = nullptr;
 }
 
@@ -259,6 +265,7 @@ extern "C" void mg_close(mg_ctx *ctx) {
     if (ctx->h_ctr_pin) hipHostFree(ctx->h_ctr_pin);
     for (void *p : ctx->retired_host) hipHostFree(p);
     if (ctx->h_xfer) hipHostFree(ctx->h_xfer);
+    if (ctx->h_ectr) hipHostFree(ctx->h_ectr);
     if (ctx->stream) hipStreamDestroy(ctx->stream);
     delete ctx;
 }
@@ -1451,6 +1458,151 @@ extern "C" int mg_step_until(mg_ctx *ctx, const uint64_t hook_mask[4], uint32_t 
         stats->kernel_ms = ms;
         stats->launches = 1;
     }
+    return MG_OK;
+}
+
+// ---- mg_explore (lane_explore.cuh) --------------------------------------------
+extern "C" int mg_explore_alloc(mg_ctx *ctx, uint32_t path_cap) {
+    if (!ctx) return MG_EINVAL;
+    if (!ctx->have_lanes) return set_err(ctx, MG_ESTATE, "mg_explore_alloc before mg_lanes_alloc");
+    if (!ctx->S.node) return set_err(ctx, MG_ESTATE, "mg_explore_alloc needs symbolic planes (mg_sym_alloc)");
+    if (ctx->E.path) return set_err(ctx, MG_ESTATE, "mg_explore_alloc: already allocated for this batch");
+    if (path_cap == 0u || path_cap > 65536u) return set_err(ctx, MG_EINVAL, "mg_explore_alloc: bad path capacity");
+    HIPX(ctx, hipSetDevice(ctx->device));
+    if (!ctx->h_ectr) {
+        if (hipHostMalloc((void **)&ctx->h_ectr, sizeof(ExploreCtr), hipHostMallocDefault) != hipSuccess)
+            return set_err(ctx, MG_ENOMEM, "mg_explore_alloc: pinned counter block");
+    }
+    DevExplore E{};
+    E.path_cap = path_cap;
+    const size_t N = ctx->L.N;
+    auto get = [&](void **p, size_t bytes) -> int {
+        if (hipMalloc(p, bytes) != hipSuccess) return set_err(ctx, MG_ENOMEM, "mg_explore_alloc: %zu bytes", bytes);
+        ctx->lane_allocs.push_back(*p);
+        return hipMemsetAsync(*p, 0, bytes, ctx->stream) == hipSuccess ? MG_OK : MG_EDEVICE;
+    };
+    int rc;
+    uint32_t *scratch = nullptr;        // path_len, root, isfree, free, kind, r1, r2, lcond, ljidx: [N] each
+    if ((rc = get((void **)&E.path, (size_t)path_cap * N * 4))) return rc;
+    if ((rc = get((void **)&scratch, (size_t)9u * N * 4))) return rc;
+    if ((rc = get((void **)&E.fork, (size_t)8u * N * 4))) return rc;
+    if ((rc = get((void **)&E.bt, (size_t)EX_MAX_BLOCKS * 6u * 4))) return rc;
+    if ((rc = get((void **)&ctx->d_ectr, sizeof(ExploreCtr)))) return rc;
+    E.path_len = scratch; E.root = scratch + N; E.isfree = scratch + 2u * N; E.free = scratch + 3u * N;
+    E.kind = scratch + 4u * N; E.r1 = scratch + 5u * N; E.r2 = scratch + 6u * N;
+    E.lcond = scratch + 7u * N; E.ljidx = scratch + 8u * N;
+    E.boff = E.bt + 4u * EX_MAX_BLOCKS;
+    HIPX(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->E = E;
+    return MG_OK;
+}
+
+// Per round: the stepping launch(es), three plan kernels, one D2H copy of the
+// counter block and one stream synchronisation, then at most three fork kernels.
+extern "C" int mg_explore(mg_ctx *ctx, const uint64_t hook_mask[4], uint32_t max_steps, uint32_t max_depth,
+                          uint32_t max_rounds, const uint32_t *free_lanes, uint32_t n_free,
+                          mg_explore_stats *stats) {
+    if (!ctx) return MG_EINVAL;
+    if (stats) *stats = mg_explore_stats{};
+    if (!ctx->have_lanes) return set_err(ctx, MG_ESTATE, "mg_explore before mg_lanes_alloc");
+    if (!ctx->uploaded) return set_err(ctx, MG_ESTATE, "mg_explore before mg_lanes_upload");
+    if (!ctx->S.node) return set_err(ctx, MG_ESTATE, "mg_explore needs symbolic planes (mg_sym_alloc)");
+    if (!ctx->E.path) return set_err(ctx, MG_ESTATE, "mg_explore needs explore planes (mg_explore_alloc)");
+    if (max_rounds == 0u) return set_err(ctx, MG_EINVAL, "mg_explore: max_rounds is 0 (the loop is bounded by it)");
+    const uint32_t n = ctx->L.n, N = ctx->L.N;
+    if (n_free && !free_lanes) return set_err(ctx, MG_EINVAL, "mg_explore: free_lanes is null with n_free = %u", n_free);
+    for (uint32_t j = 0; j < n_free; ++j) {
+        if (free_lanes[j] >= n)
+            return set_err(ctx, MG_EINVAL, "mg_explore: free_lanes[%u] = %u outside batch of %u", j, free_lanes[j], n);
+        if (j && free_lanes[j] <= free_lanes[j - 1u])
+            return set_err(ctx, MG_EINVAL, "mg_explore: free_lanes[%u] = %u is not above free_lanes[%u] = %u", j,
+                           free_lanes[j], j - 1u, free_lanes[j - 1u]);
+    }
+    HIPX(ctx, hipSetDevice(ctx->device));
+    const DevExplore &E = ctx->E;
+    int rc;
+    if (n_free) {
+        if ((rc = ensure_hxfer(ctx, (size_t)n_free * 4u))) return rc;
+        std::memcpy(ctx->h_xfer, free_lanes, (size_t)n_free * 4u);
+        HIPX(ctx, hipMemcpyAsync(E.free, ctx->h_xfer, (size_t)n_free * 4u, hipMemcpyHostToDevice, ctx->stream));
+    }
+    HIPX(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    hipLaunchKernelGGL(k_explore_init, dim3(blocks_for(n)), dim3(256), 0, ctx->stream, E, n);
+    if (n_free) hipLaunchKernelGGL(k_explore_mark, dim3(blocks_for(n_free)), dim3(256), 0, ctx->stream, E, n_free);
+    HIPX(ctx, hipGetLastError());
+    // block b of the plan owns lanes [b * chunk, (b + 1) * chunk): at most EX_MAX_BLOCKS totals
+    const uint32_t tiles = blocks_for(n);
+    const uint32_t chunk = ((tiles + EX_MAX_BLOCKS - 1u) / EX_MAX_BLOCKS) * 256u;
+    const uint32_t nb = (n + chunk - 1u) / chunk;
+    const uint32_t n_step_ctr = blocks_for(n, lane_block(ctx));
+    ForkArgs F{};
+    F.n_codes = (uint32_t)ctx->codes.size(); F.cov_on = ctx->cfg.coverage ? 1u : 0u;
+    F.src = E.fork; F.dst_fall = E.fork + N; F.dst_jump = E.fork + 2u * (size_t)N;
+    F.copy_fork = E.fork + 3u * (size_t)N; F.copy_dst = E.fork + 4u * (size_t)N;
+    F.made = E.fork + 5u * (size_t)N; F.cond = E.fork + 6u * (size_t)N; F.jidx = E.fork + 7u * (size_t)N;
+    mg_explore_stats st{};
+    uint32_t used = 0u;
+    for (uint32_t round = 0; round < max_rounds; ++round) {
+        if ((rc = launch_step(ctx, hook_mask, max_steps, max_depth, ctx->d_ctr))) return rc;
+        const uint32_t avail = n_free - used;
+        hipLaunchKernelGGL(k_explore_scan, dim3(nb), dim3(256), 0, ctx->stream, ctx->L, ctx->S, E, ctx->d_codes,
+                           ctx->d_a8, ctx->d_a32, F.n_codes, chunk);
+        hipLaunchKernelGGL(k_explore_totals, dim3(1), dim3(EX_MAX_BLOCKS), 0, ctx->stream, E, nb, avail, ctx->d_ctr,
+                           n_step_ctr, ctx->d_ectr);
+        hipLaunchKernelGGL(k_explore_emit, dim3(tiles), dim3(256), 0, ctx->stream, E, n, N, chunk, used, avail);
+        HIPX(ctx, hipGetLastError());
+        HIPX(ctx, hipMemcpyAsync(ctx->h_ectr, ctx->d_ectr, sizeof(ExploreCtr), hipMemcpyDeviceToHost, ctx->stream));
+        HIPX(ctx, hipStreamSynchronize(ctx->stream));
+        const ExploreCtr c = *ctx->h_ectr;
+        if (c.forks > n || c.copies > avail || c.copies > c.forks)
+            return set_err(ctx, MG_EDEVICE, "mg_explore: plan of %u forks and %u copies over %u lanes and %u free",
+                           c.forks, c.copies, n, avail);
+        st.rounds += 1u; st.forks += c.forks; st.made_jump += c.copies; st.starved += c.starved;
+        st.path_full += c.path_full; st.lane_steps += c.lane_steps;
+        used += c.copies;
+        st.running = c.running + c.forks + c.copies;
+        if (c.forks) {
+            F.n = c.forks; F.n_copies = c.copies;
+            if (c.copies) {
+                const uint32_t ct = (c.copies + 63u) / 64u;
+                const uint32_t gy = std::min<uint32_t>(std::max<uint32_t>(1024u / ct, 1u), 64u);
+                hipLaunchKernelGGL(k_fork_copy, dim3(ct, gy), dim3(64, 4), 0, ctx->stream, ctx->L, ctx->S, F);
+            }
+            hipLaunchKernelGGL(k_fork_commit, dim3(blocks_for(c.forks)), dim3(256), 0, ctx->stream, ctx->L, ctx->S,
+                               ctx->d_codes, ctx->d_a8, ctx->d_cov, F);
+            hipLaunchKernelGGL(k_explore_path, dim3(blocks_for(c.forks)), dim3(256), 0, ctx->stream, E, N, F);
+            HIPX(ctx, hipGetLastError());
+        } else if (c.running == 0u) {
+            break;
+        }
+    }
+    HIPX(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+    HIPX(ctx, hipStreamSynchronize(ctx->stream));
+    st.free_used = used;
+    HIPX(ctx, hipEventElapsedTime(&st.kernel_ms, ctx->ev0, ctx->ev1));
+    if (stats) *stats = st;
+    return MG_OK;
+}
+
+// path comes out lane-major, [n][path_cap]; entries at and above a lane's path_len are 0
+extern "C" int mg_explore_download(mg_ctx *ctx, uint32_t *path, uint32_t *path_len, uint32_t *root, uint32_t first,
+                                   uint32_t n) {
+    if (!ctx) return MG_EINVAL;
+    if (!ctx->E.path) return set_err(ctx, MG_ESTATE, "mg_explore_download before mg_explore_alloc");
+    if (first + (uint64_t)n > ctx->L.n)
+        return set_err(ctx, MG_EINVAL, "path range [%u,%u) outside batch of %u", first, first + n, ctx->L.n);
+    if (n == 0u) return MG_OK;
+    if (!path || !path_len || !root) return set_err(ctx, MG_EINVAL, "mg_explore_download: path, path_len and root are required");
+    HIPX(ctx, hipSetDevice(ctx->device));
+    const DevExplore &E = ctx->E;
+    const size_t N = ctx->L.N, cap = E.path_cap;
+    std::vector<uint32_t> rows(cap * (size_t)n);
+    HIPX(ctx, hipStreamSynchronize(ctx->stream));
+    HIPX(ctx, hipMemcpy(path_len, E.path_len + first, (size_t)n * 4u, hipMemcpyDeviceToHost));
+    HIPX(ctx, hipMemcpy(root, E.root + first, (size_t)n * 4u, hipMemcpyDeviceToHost));
+    HIPX(ctx, hipMemcpy2D(rows.data(), (size_t)n * 4u, E.path + first, N * 4u, (size_t)n * 4u, cap, hipMemcpyDeviceToHost));
+    for (uint32_t i = 0; i < n; ++i)
+        for (size_t e = 0; e < cap; ++e) path[(size_t)i * cap + e] = e < path_len[i] ? rows[e * n + i] : 0u;
     return MG_OK;
 }
 

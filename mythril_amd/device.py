@@ -26,6 +26,19 @@ class StepStats:
     kernel_ms: float
 
 
+@dataclass
+class ExploreStats:
+    rounds: int
+    forks: int
+    made_jump: int
+    starved: int
+    path_full: int
+    free_used: int
+    running: int
+    lane_steps: int
+    kernel_ms: float
+
+
 def _mask_array(hook_mask: Optional[Sequence[int]]):
     m = list(hook_mask) if hook_mask is not None else [0, 0, 0, 0]
     return (ctypes.c_uint64 * 4)(*[int(x) & ((1 << 64) - 1) for x in m])
@@ -48,6 +61,7 @@ class GpuDevice:
             raise native.MythGpuError(f"mg_open({device}) failed with {rc}")
         self.device = device
         self.shape: Optional[LaneShape] = None
+        self.path_cap = 0                  # explore planes of the current batch (explore_alloc)
         self.codes = []
 
     # -- errors --------------------------------------------------------------
@@ -108,6 +122,7 @@ class GpuDevice:
         if shape.obj_cap:
             self._check(self.lib.mg_taint_alloc(self.ctx, shape.obj_cap), "mg_taint_alloc")
         self.shape = shape
+        self.path_cap = 0
 
     def set_taint_program(self, actions) -> None:
         """mg_taint_program: the per-opcode action words of the batch-safe hooks
@@ -194,6 +209,35 @@ class GpuDevice:
         self._check(self.lib.mg_lanes_fork(self.ctx, ctypes.byref(batch), made.ctypes.data, cond.ctypes.data,
                                            ctypes.byref(ms)), "mg_lanes_fork")
         return made, cond, ms.value
+
+    def explore_alloc(self, path_cap: int):
+        """mg_explore_alloc: the path planes of mg_explore, `path_cap` entries per
+        lane; after alloc() of a shape with symbolic planes, once per batch."""
+        self._check(self.lib.mg_explore_alloc(self.ctx, int(path_cap)), "mg_explore_alloc")
+        self.path_cap = int(path_cap)
+
+    def explore(self, free, hook_mask=None, max_steps: int = 1 << 30, max_depth: int = 0,
+                max_rounds: int = 64) -> ExploreStats:
+        """mg_explore: up to `max_rounds` rounds of step + fork on the device.  `free`:
+        the lanes that may be overwritten with jump successors, strictly ascending;
+        they are handed out from the front, stats.free_used of them."""
+        arr = np.ascontiguousarray(np.asarray(free, dtype=np.uint32).reshape(-1))
+        st = native.MgExploreStats()
+        self._check(self.lib.mg_explore(self.ctx, _mask_array(hook_mask), max_steps, max_depth, int(max_rounds),
+                                        arr.ctypes.data if arr.size else None, arr.size, ctypes.byref(st)),
+                    "mg_explore")
+        return ExploreStats(st.rounds, st.forks, st.made_jump, st.starved, st.path_full, st.free_used, st.running,
+                            st.lane_steps, st.kernel_ms)
+
+    def explore_paths(self, first: int, n: int):
+        """mg_explore_download: (path uint32[n, path_cap] of cond_tag << 1 | side,
+        zero at and above path_len; path_len uint32[n]; root uint32[n])."""
+        path = np.zeros((n, self.path_cap), dtype=np.uint32)
+        path_len = np.zeros(n, dtype=np.uint32)
+        root = np.zeros(n, dtype=np.uint32)
+        self._check(self.lib.mg_explore_download(self.ctx, path.ctypes.data, path_len.ctypes.data, root.ctypes.data,
+                                                 first, n), "mg_explore_download")
+        return path, path_len, root
 
     def step(self, hook_mask=None, max_steps: int = 1 << 30, max_depth: int = 0,
              horizon: int = 0) -> StepStats:

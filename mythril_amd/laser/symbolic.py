@@ -819,6 +819,28 @@ def fork_conditions(b, i: int, state, cond_tag: int):
     return negated, condi
 
 
+def path_constraints(b, lane: int, state, path_row):
+    """The constraints a lane gained on the path mg_explore recorded for it:
+    `path_row` holds its entries (cond_tag << 1 | side, oldest first; the live
+    ones only), `b` the downloaded image, `state` the state its lineage's root
+    was packed from.  Each entry's node is decoded from lane `lane`'s own arena
+    (every descendant keeps it at that index) and fork_conditions' rules are
+    applied in order: the jump side appends `condi`, the fall-through `negated`,
+    and a condition whose value is True is not appended.  None when any entry's
+    condition is_false: the reference never makes that successor, the device
+    cannot know it, and the caller drops the lane."""
+    out = []
+    for entry in path_row:
+        entry = int(entry)
+        negated, condi = fork_conditions(b, lane, state, entry >> 1)
+        c = condi if entry & 1 else negated
+        if c.is_false:
+            return None
+        if c.value is not True:
+            out.append(c)
+    return out
+
+
 def _fork_copy(state):
     """deepcopy(global_state) of the reference's fork (world state, machine
     state and account copies; expressions are immutable and shared)."""

@@ -114,6 +114,13 @@ class MgForkBatch(ctypes.Structure):
                 ("dst_fall", ctypes.c_void_p), ("dst_jump", ctypes.c_void_p)]
 
 
+class MgExploreStats(ctypes.Structure):
+    _fields_ = [("rounds", ctypes.c_uint32), ("forks", ctypes.c_uint32), ("made_jump", ctypes.c_uint32),
+                ("starved", ctypes.c_uint32), ("path_full", ctypes.c_uint32), ("free_used", ctypes.c_uint32),
+                ("running", ctypes.c_uint32), ("_pad", ctypes.c_uint32), ("lane_steps", ctypes.c_uint64),
+                ("kernel_ms", ctypes.c_float), ("_padf", ctypes.c_float)]
+
+
 # every symbol include/mythgpu.h declares: name -> (restype, argtypes)
 _P, _U32, _U64, _I = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int
 _PU32 = ctypes.POINTER(ctypes.c_uint32)
@@ -139,6 +146,9 @@ SIGNATURES = {
     "mg_lanes_upload_live": (_I, [_P, _P, _U32, _U32]),
     "mg_lanes_reset": (_I, [_P]),
     "mg_lanes_fork": (_I, [_P, ctypes.POINTER(MgForkBatch), _P, _P, ctypes.POINTER(ctypes.c_float)]),
+    "mg_explore_alloc": (_I, [_P, _U32]),
+    "mg_explore": (_I, [_P, _P, _U32, _U32, _U32, _P, _U32, ctypes.POINTER(MgExploreStats)]),
+    "mg_explore_download": (_I, [_P, _P, _P, _P, _U32, _U32]),
     "mg_step": (_I, [_P, _P, _U32, _U32, ctypes.POINTER(MgStepStats)]),
     "mg_step_async": (_I, [_P, _P, _U32, _U32]),
     "mg_run_batches": (_I, [_P, _P, _U32, _U32, _U32, ctypes.POINTER(MgStepStats)]),
