@@ -63,7 +63,8 @@ extern "C" {
                                   mg_code_fentries): the last JUMP / JUMPI landing
                                   on a dispatcher entry, for active_function_name;
                                   additive: mg_eval_terms, mg_eval_min, mg_lanes_fork,
-                                  mg_explore_alloc / mg_explore / mg_explore_download */
+                                  mg_explore_alloc / mg_explore / mg_explore_download,
+                                  mg_explore_upload, mg_explore_check */
 
 /* ------------------------------------------------------------------ errors */
 #define MG_OK          0
@@ -648,6 +649,102 @@ int         mg_explore(mg_ctx *ctx, const uint64_t hook_mask[4], uint32_t max_st
 int         mg_explore_download(mg_ctx *ctx, uint32_t *path /* [n][path_cap] */,
                                 uint32_t *path_len /* [n] */, uint32_t *root /* [n] */,
                                 uint32_t first, uint32_t n);
+/* The inverse of mg_explore_download, for a caller that keeps paths of its own
+ * (a host-made fork, a test's hand-written image): lanes [first, first + n) take
+ * path (lane-major, [n][path_cap]; entries at and above path_len[i] are not
+ * read), path_len and root.  MG_ESTATE without explore planes; MG_EINVAL, with
+ * nothing written, for a range outside the batch, a NULL array with n > 0 or a
+ * path_len above path_cap.  root is data: mg_explore_check answers a root outside
+ * the batch with MG_PATH_UNKNOWN.  The next mg_explore restarts every lane's path. */
+int         mg_explore_upload(mg_ctx *ctx, const uint32_t *path /* [n][path_cap] */,
+                              const uint32_t *path_len /* [n] */, const uint32_t *root /* [n] */,
+                              uint32_t first, uint32_t n);
+
+/* The fork filter's question, "does any cached model satisfy this lane's path"
+ * (svm.py:319-326 -> ModelCache.check_quick_sat, support_utils.py:60-68), answered
+ * where the arena is: every path entry of a lane is evaluated straight from the
+ * lane's arena under every candidate model, with no download, decode or flatten.
+ * The verdict has mg_eval_bits' meaning; the host decodes and flattens only the
+ * lanes no candidate satisfies or whose path the device cannot evaluate.
+ *
+ * It needs mg_sym_alloc and mg_explore_alloc (MG_ESTATE otherwise) and reads the
+ * device image as the last mg_explore (or mg_explore_upload) left it: path,
+ * path_len, root, the arena, the constants, the storage chain and its tags.  It
+ * writes nothing of the image.  For lane l in [first, first + n) with binding
+ * b = lane_binding[root[l]]:
+ *   first_sat[l - first] = the smallest model m with bit m of allowed[b] set (NULL
+ *     allowed: every model) under which EVERY path entry holds; MG_BV_NO_MODEL when
+ *     there is none; MG_PATH_UNKNOWN when the lane is unknown (below);
+ *   sat_bits (may be NULL) has mg_eval_bits' layout, one bit per satisfying allowed
+ *     model; all zero for an unknown lane.
+ * A lane with path_len == 0 is satisfied by every allowed model.  `allowed`
+ * carries what does not depend on the path (the lineage's initial constraints,
+ * the keccak conjunct): the sat_bits rows mg_eval_bits gave for them, unchanged.
+ * An entry (cond_tag, side) with condition node c = cond_tag - 1 holds when
+ * (value(c) != 0) == (side == 1): fork_conditions' rules.  models == NULL uses the
+ * pool the last mg_eval_upload (or mg_eval*, or mg_explore_check with models) left
+ * resident; otherwise the models are uploaded as mg_eval uploads them, and the
+ * programs of an earlier mg_eval_upload are dropped (mg_eval_run then gives
+ * MG_ESTATE: they may name variables the new pool does not have).
+ *
+ * The value of a node under model m is an integer masked to the node's width
+ * (x >> 8, 1..256), the value of the term the host's decoder builds for the node
+ * as kernel 2 computes it (z3's x / 0, x mod 0, signed division and shifts >= the
+ * width are kernel 2's).  An operand ref with MG_SYM_CONST is the lane's constant,
+ * otherwise a node's value; a node only refers to nodes below itself.
+ *   MG_SYM_CDSIZE        values[var_cdsize][m]
+ *   MG_SYM_ENV, w < MG_ENV_WORDS   values[var_env[w]][m]
+ *   calldata byte at the 256-bit index i: i < size (signed, as state/calldata.py's
+ *     bound check) ? table tab_calldata at i : 0
+ *   MG_SYM_CDLOAD(y)     the big-endian bytes at value(y) + k mod 2^256, k = 0..31
+ *   MG_SYM_CDBYTE        the byte at w;  MG_SYM_CDBYTEX: at value(y) + w mod 2^256
+ *   MG_SYM_BIN           ADD MUL SUB; DIV SDIV MOD SMOD = bvudiv bvsdiv bvurem
+ *     bvsrem; LT GT (unsigned) SLT SGT EQ (0 / 1); AND OR XOR; BYTE with a constant
+ *     index y below 32; SHL SHR SAR with the amount in y
+ *   MG_SYM_UN            ISZERO: value(y) == 0; NOT: the complement at the width
+ *   MG_SYM_EXTRACT       bits w >> 16 .. w & 0xffff of node y (the node's width is
+ *     their count); MG_SYM_CONCAT: y high, z low, widths w & 0xffff and w >> 16
+ *     (the node's width is their sum, at most 256)
+ *   MG_SYM_SLOAD(y, z)   the store chain walked from entry z - 1 down to 0: the
+ *     first entry whose key's value equals value(y) gives its value's value (a tag
+ *     of 0: the limbs of the storage row, else node tag - 1); no match: table
+ *     tab_storage at value(y) on an MG_LANE_SYMSTORE lane, else 0
+ * A lane is MG_PATH_UNKNOWN -- a normal answer, one per lane whatever the model --
+ * when the cone of its path's condition nodes (what operand refs and, for SLOAD,
+ * the store-chain tags reach) holds MG_SYM_KECCAK, MG_SYM_TERM, MG_SYM_MLOADK,
+ * MG_SYM_MSTOREK or MG_SYM_BALANCE; an MG_SYM_ENV with w >= MG_ENV_WORDS; a BIN /
+ * UN opcode not listed (EXP's Power), a BYTE whose index is no constant below 32,
+ * an unknown kind or a width outside what is stated above; a symbol whose binding
+ * field is MG_PATH_UNBOUND, a lineage whose lane_binding is MG_PATH_UNBOUND or a
+ * root outside the batch; a reference at or past n_nodes / n_consts or not below
+ * the referring node, z above the lane's storage_count, a cond_tag of 0, or an
+ * arena of more than MG_PATH_MAX_NODES nodes.  Every index the kernel follows is
+ * checked against the lane's counts and the planes' capacities before it is used.
+ * Nodes outside the cone never matter.
+ *
+ * Checked on the host (MG_EINVAL, nothing launched, nothing written): an entry of
+ * lane_binding that is neither below n_bindings nor MG_PATH_UNBOUND; a binding's
+ * variable / table index that is neither below the pool's counts nor
+ * MG_PATH_UNBOUND; first + n > n_lanes; NULL first_sat, bindings (with
+ * n_bindings > 0) or lane_binding with n > 0; a pool of no models.  n == 0
+ * succeeds.  The number of launches and copies does not depend on n.          */
+#define MG_PATH_UNKNOWN 0xfffffffeu   /* first_sat[]: the path needs a term the device does not evaluate */
+#define MG_PATH_UNBOUND 0xffffffffu   /* a binding field / lane_binding[]: nothing bound */
+#define MG_PATH_MAX_NODES 65536u      /* largest arena (n_nodes) mg_explore_check evaluates */
+typedef struct mg_path_binding {      /* where one lineage's symbols live in the model batch */
+    uint32_t var_cdsize;              /* {id}_calldatasize: index into models->values */
+    uint32_t tab_calldata;            /* {id}_calldata: table index (Array 256 -> 8) */
+    uint32_t var_env[MG_ENV_WORDS];   /* by MG_ENV_ADDRESS .. MG_ENV_GASPRICE */
+    uint32_t tab_storage;             /* Storage{addr} (Array 256 -> 256) for MG_LANE_SYMSTORE lanes */
+} mg_path_binding;
+struct mg_model_batch;
+int         mg_explore_check(mg_ctx *ctx, const struct mg_model_batch *models,
+                             const mg_path_binding *bindings, uint32_t n_bindings,
+                             const uint32_t *lane_binding /* [n_lanes], indexed by root[lane] */,
+                             const uint64_t *allowed /* [n_bindings][ceil(n_models/64)] or NULL */,
+                             uint32_t first, uint32_t n,
+                             uint32_t *first_sat /* [n] */, uint64_t *sat_bits /* [n][ceil(n_models/64)] or NULL */,
+                             float *kernel_ms);
 
 /* Replaces the LaserEVM.exec() drain for device-eligible lanes (svm.py:293-337
  * + execute_state svm.py:369-491 + Instruction.evaluate instructions.py:235-267):

@@ -578,16 +578,73 @@ static void bv_fuse(const mg_dag_batch *dags, std::vector<uint32_t> &out, std::v
     off[n] = (uint32_t)(out.size() / 4);
 }
 
-static int bv_upload(BvState &s, const mg_dag_batch *dags, const mg_model_batch *models, hipStream_t st,
-                     std::string &msg) {
-    if (dags->n_dags == 0 || !dags->prog_off || !dags->insns) { msg = "empty DAG batch"; return MG_EINVAL; }
-    if (dags->n_slots > MG_BV_MAX_SLOTS) { msg = "too many slots"; return MG_EINVAL; }
-    if ((uint64_t)dags->n_consts * 32u >= (1ull << 32)) { msg = "constant table over 4 GiB"; return MG_EINVAL; }
+// The model half of an upload, shared by bv_upload (mg_eval*) and mg_explore_check's
+// models argument (path_eval.cuh): check the sizes, check the tables, allocate,
+// enqueue the copies, commit the counts.
+static int bv_models_check(const mg_model_batch *models, std::string &msg) {
     if (models->n_models == 0 || (models->n_vars && !models->values)) { msg = "empty model batch"; return MG_EINVAL; }
     if ((uint64_t)models->n_vars * models->n_models * 32u >= (1ull << 32)) {
         msg = "model values over 4 GiB (variables x models x 32 bytes)";     // the kernel's 32-bit offsets
         return MG_EINVAL;
     }
+    return 0;
+}
+static int bv_tables_check(const mg_model_batch *models, std::string &msg) {
+    if (models->n_tables) {
+        if (!models->tab_start || !models->tab_count || !models->tab_default ||
+            (models->n_entries && !models->tab_entries)) { msg = "table arrays missing"; return MG_EINVAL; }
+        const size_t tm = (size_t)models->n_tables * models->n_models;
+        for (size_t k = 0; k < tm; ++k)
+            if ((uint64_t)models->tab_start[k] + models->tab_count[k] > models->n_entries) {
+                msg = "table entries out of range"; return MG_EINVAL;
+            }
+    }
+    return 0;
+}
+static int bv_models_alloc(BvState &s, const mg_model_batch *models, std::string &msg) {
+    int rc = 0;
+    if ((rc = bv_ensure(s.values, s.cap_values, (size_t)std::max<uint32_t>(models->n_vars, 1) * models->n_models * 2))) { msg = "alloc values"; return rc; }
+    if (models->n_tables) {
+        const size_t tm = (size_t)models->n_tables * models->n_models;
+        hipFree(s.tab_start); hipFree(s.tab_count); hipFree(s.tab_default);
+        s.tab_start = s.tab_count = nullptr;
+        s.tab_default = nullptr;
+        if (hipMalloc(&s.tab_start, tm * 4) != hipSuccess || hipMalloc(&s.tab_count, tm * 4) != hipSuccess ||
+            hipMalloc(&s.tab_default, tm * 64) != hipSuccess) {
+            msg = "alloc tables"; return MG_ENOMEM;
+        }
+        if ((rc = bv_ensure(s.tab_entries, s.cap_entries, (size_t)std::max<uint32_t>(models->n_entries, 1) * 8))) {
+            msg = "alloc table entries"; return rc;
+        }
+    }
+    return 0;
+}
+static hipError_t bv_models_copy(BvState &s, const mg_model_batch *models, hipStream_t st) {
+    hipError_t e = hipSuccess;
+    if (models->n_vars)
+        e = e ? e : hipMemcpyAsync(s.values, models->values, (size_t)models->n_vars * models->n_models * 32, hipMemcpyHostToDevice, st);
+    if (models->n_tables) {
+        const size_t tm = (size_t)models->n_tables * models->n_models;
+        e = e ? e : hipMemcpyAsync(s.tab_start, models->tab_start, tm * 4, hipMemcpyHostToDevice, st);
+        e = e ? e : hipMemcpyAsync(s.tab_count, models->tab_count, tm * 4, hipMemcpyHostToDevice, st);
+        e = e ? e : hipMemcpyAsync(s.tab_default, models->tab_default, tm * 64, hipMemcpyHostToDevice, st);
+        if (models->n_entries)
+            e = e ? e : hipMemcpyAsync(s.tab_entries, models->tab_entries, (size_t)models->n_entries * 128,
+                                       hipMemcpyHostToDevice, st);
+    }
+    return e;
+}
+static void bv_models_commit(BvState &s, const mg_model_batch *models) {
+    s.n_tables = models->n_tables; s.n_entries = models->n_entries;
+    s.n_models = models->n_models; s.n_vars = models->n_vars;
+}
+
+static int bv_upload(BvState &s, const mg_dag_batch *dags, const mg_model_batch *models, hipStream_t st,
+                     std::string &msg) {
+    if (dags->n_dags == 0 || !dags->prog_off || !dags->insns) { msg = "empty DAG batch"; return MG_EINVAL; }
+    if (dags->n_slots > MG_BV_MAX_SLOTS) { msg = "too many slots"; return MG_EINVAL; }
+    if ((uint64_t)dags->n_consts * 32u >= (1ull << 32)) { msg = "constant table over 4 GiB"; return MG_EINVAL; }
+    if (int mrc = bv_models_check(models, msg)) return mrc;
     const uint32_t n = dags->n_dags;
     const uint32_t total = dags->prog_off[n];
     // validate programs on the host: refs in range, program fits a tile
@@ -630,15 +687,7 @@ static int bv_upload(BvState &s, const mg_dag_batch *dags, const mg_model_batch 
     }
     // the models' tables too, before anything of the previous upload is replaced: a
     // refused batch leaves that upload whole (mg_eval_run on it stays valid)
-    if (models->n_tables) {
-        if (!models->tab_start || !models->tab_count || !models->tab_default ||
-            (models->n_entries && !models->tab_entries)) { msg = "table arrays missing"; return MG_EINVAL; }
-        const size_t tm = (size_t)models->n_tables * models->n_models;
-        for (size_t k = 0; k < tm; ++k)
-            if ((uint64_t)models->tab_start[k] + models->tab_count[k] > models->n_entries) {
-                msg = "table entries out of range"; return MG_EINVAL;
-            }
-    }
+    if (int trc = bv_tables_check(models, msg)) return trc;
     const char *fv = getenv("MG_BV_FUSE");
     const uint32_t *insns = dags->insns, *prog_off = dags->prog_off;
     uint32_t total_up = total;
@@ -676,26 +725,7 @@ static int bv_upload(BvState &s, const mg_dag_batch *dags, const mg_model_batch 
     if ((rc = bv_ensure(s.prog_off, s.cap_dags, (size_t)n + 1))) { msg = "alloc offsets"; return rc; }
     if ((rc = bv_ensure(s.tile_dag, s.cap_tiles, s.h_tiles.size()))) { msg = "alloc tiles"; return rc; }
     if ((rc = bv_ensure(s.consts, s.cap_consts, (size_t)std::max<uint32_t>(dags->n_consts, 1) * 2))) { msg = "alloc consts"; return rc; }
-    if ((rc = bv_ensure(s.values, s.cap_values, (size_t)std::max<uint32_t>(models->n_vars, 1) * models->n_models * 2))) { msg = "alloc values"; return rc; }
-    if (models->n_tables) {
-        if (!models->tab_start || !models->tab_count || !models->tab_default ||
-            (models->n_entries && !models->tab_entries)) { msg = "table arrays missing"; return MG_EINVAL; }
-        const size_t tm = (size_t)models->n_tables * models->n_models;
-        for (size_t k = 0; k < tm; ++k)
-            if ((uint64_t)models->tab_start[k] + models->tab_count[k] > models->n_entries) {
-                msg = "table entries out of range"; return MG_EINVAL;
-            }
-        hipFree(s.tab_start); hipFree(s.tab_count); hipFree(s.tab_default);
-        s.tab_start = s.tab_count = nullptr;
-        s.tab_default = nullptr;
-        if (hipMalloc(&s.tab_start, tm * 4) != hipSuccess || hipMalloc(&s.tab_count, tm * 4) != hipSuccess ||
-            hipMalloc(&s.tab_default, tm * 64) != hipSuccess) {
-            msg = "alloc tables"; return MG_ENOMEM;
-        }
-        if ((rc = bv_ensure(s.tab_entries, s.cap_entries, (size_t)std::max<uint32_t>(models->n_entries, 1) * 8))) {
-            msg = "alloc table entries"; return rc;
-        }
-    }
+    if ((rc = bv_models_alloc(s, models, msg))) return rc;
     hipFree(s.first_sat); hipFree(s.sat_count);
     s.first_sat = s.sat_count = nullptr;
     if (hipMalloc(&s.first_sat, (size_t)n * 4) != hipSuccess || hipMalloc(&s.sat_count, (size_t)n * 4) != hipSuccess) {
@@ -707,21 +737,11 @@ static int bv_upload(BvState &s, const mg_dag_batch *dags, const mg_model_batch 
     e = e ? e : hipMemcpyAsync(s.prog_off, prog_off, ((size_t)n + 1) * 4, hipMemcpyHostToDevice, st);
     e = e ? e : hipMemcpyAsync(s.tile_dag, s.h_tiles.data(), s.h_tiles.size() * 4, hipMemcpyHostToDevice, st);
     if (dags->n_consts) e = e ? e : hipMemcpyAsync(s.consts, dags->consts, (size_t)dags->n_consts * 32, hipMemcpyHostToDevice, st);
-    if (models->n_vars)
-        e = e ? e : hipMemcpyAsync(s.values, models->values, (size_t)models->n_vars * models->n_models * 32, hipMemcpyHostToDevice, st);
-    if (models->n_tables) {
-        const size_t tm = (size_t)models->n_tables * models->n_models;
-        e = e ? e : hipMemcpyAsync(s.tab_start, models->tab_start, tm * 4, hipMemcpyHostToDevice, st);
-        e = e ? e : hipMemcpyAsync(s.tab_count, models->tab_count, tm * 4, hipMemcpyHostToDevice, st);
-        e = e ? e : hipMemcpyAsync(s.tab_default, models->tab_default, tm * 64, hipMemcpyHostToDevice, st);
-        if (models->n_entries)
-            e = e ? e : hipMemcpyAsync(s.tab_entries, models->tab_entries, (size_t)models->n_entries * 128,
-                                       hipMemcpyHostToDevice, st);
-    }
+    e = e ? e : bv_models_copy(s, models, st);
     e = e ? e : hipStreamSynchronize(st);
     if (e != hipSuccess) { msg = std::string("bv upload: ") + hipGetErrorString(e); return MG_EDEVICE; }
-    s.n_tables = models->n_tables; s.n_entries = models->n_entries;
-    s.n_dags = n; s.n_models = models->n_models; s.n_vars = models->n_vars;
+    bv_models_commit(s, models);
+    s.n_dags = n;
     s.n_slots = std::max<uint32_t>(dags->n_slots, 1); s.n_consts = dags->n_consts;
     return 0;
 }

@@ -22,6 +22,7 @@
 #include "sym_step.cuh"
 #include "lane_fork.cuh"
 #include "lane_explore.cuh"
+#include "path_eval.cuh"
 #include "cc.h"
 
 // ------------------------------------------------------------------ context
@@ -52,6 +53,11 @@ struct mg_ctx {
     DevExplore E{};                      // path planes and plan scratch (mg_explore_alloc), freed with the lanes
     ExploreCtr *d_ectr = nullptr;        // the round's counter block (with E)
     ExploreCtr *h_ectr = nullptr;        // its pinned host side (freed by mg_close)
+    // mg_explore_check (path_eval.cuh): the node-value workspace and the call's arrays
+    // (bindings | lane_binding | allowed | first_sat | sat_bits); outgrown ones retire
+    uint4 *d_pws = nullptr;
+    uint8_t *d_pio = nullptr;
+    size_t pws_cap = 0, pio_cap = 0;     // bytes
     uint32_t *d_tprog = nullptr;         // [256] taint action words (mg_taint_program)
     uint8_t *d_tforce = nullptr;         // per code instruction (coverage layout): host-run hooks
     size_t cap_tforce = 0;
@@ -256,6 +262,7 @@ extern "C" void mg_close(mg_ctx *ctx) {
     hipFree(ctx->d_stage);
     hipFree(ctx->d_tprog);
     hipFree(ctx->d_tforce);
+    hipFree(ctx->d_pws); hipFree(ctx->d_pio);
     hipFree(ctx->d_ktab);
     if (ctx->ev0) hipEventDestroy(ctx->ev0);
     if (ctx->ev1) hipEventDestroy(ctx->ev1);
@@ -1603,6 +1610,157 @@ extern "C" int mg_explore_download(mg_ctx *ctx, uint32_t *path, uint32_t *path_l
     HIPX(ctx, hipMemcpy2D(rows.data(), (size_t)n * 4u, E.path + first, N * 4u, (size_t)n * 4u, cap, hipMemcpyDeviceToHost));
     for (uint32_t i = 0; i < n; ++i)
         for (size_t e = 0; e < cap; ++e) path[(size_t)i * cap + e] = e < path_len[i] ? rows[e * n + i] : 0u;
+    return MG_OK;
+}
+
+extern "C" int mg_explore_upload(mg_ctx *ctx, const uint32_t *path, const uint32_t *path_len, const uint32_t *root,
+                                 uint32_t first, uint32_t n) {
+    if (!ctx) return MG_EINVAL;
+    if (!ctx->E.path) return set_err(ctx, MG_ESTATE, "mg_explore_upload before mg_explore_alloc");
+    if (first + (uint64_t)n > ctx->L.n)
+        return set_err(ctx, MG_EINVAL, "path range [%u,%u) outside batch of %u", first, first + n, ctx->L.n);
+    if (n == 0u) return MG_OK;
+    if (!path || !path_len || !root) return set_err(ctx, MG_EINVAL, "mg_explore_upload: path, path_len and root are required");
+    const DevExplore &E = ctx->E;
+    const size_t N = ctx->L.N, cap = E.path_cap;
+    for (uint32_t i = 0; i < n; ++i)
+        if (path_len[i] > cap)
+            return set_err(ctx, MG_EINVAL, "mg_explore_upload: path_len[%u] = %u above path_cap %zu", i, path_len[i], cap);
+    HIPX(ctx, hipSetDevice(ctx->device));
+    std::vector<uint32_t> rows(cap * (size_t)n);            // entry-major, as the plane; 0 above a lane's length
+    for (uint32_t i = 0; i < n; ++i)
+        for (size_t e = 0; e < cap; ++e) rows[e * n + i] = e < path_len[i] ? path[(size_t)i * cap + e] : 0u;
+    HIPX(ctx, hipStreamSynchronize(ctx->stream));
+    HIPX(ctx, hipMemcpy(E.path_len + first, path_len, (size_t)n * 4u, hipMemcpyHostToDevice));
+    HIPX(ctx, hipMemcpy(E.root + first, root, (size_t)n * 4u, hipMemcpyHostToDevice));
+    HIPX(ctx, hipMemcpy2D(E.path + first, N * 4u, rows.data(), (size_t)n * 4u, (size_t)n * 4u, cap, hipMemcpyHostToDevice));
+    return MG_OK;
+}
+
+// ---- mg_explore_check (path_eval.cuh) ------------------------------------------
+// a buffer of the path check: grown geometrically, the outgrown one retired (freed by
+// mg_close), so nothing is freed under work that may still be queued
+template <class T>
+static int path_ensure(mg_ctx *ctx, T *&p, size_t &cap, size_t bytes, const char *what) {
+    if (bytes <= cap && p) return MG_OK;
+    const size_t ncap = std::max<size_t>(bytes, cap + cap / 2u + 4096u);
+    T *q = nullptr;
+    if (hipMalloc((void **)&q, ncap) != hipSuccess) return set_err(ctx, MG_ENOMEM, "mg_explore_check: %s of %zu bytes", what, ncap);
+    if (p) ctx->retired.push_back(p);
+    p = q;
+    cap = ncap;
+    return MG_OK;
+}
+
+// One D2H copy (the checked lanes' node counts), one H2D copy (the call's arrays),
+// one memset, one launch, one D2H copy (the results): none depends on n.
+extern "C" int mg_explore_check(mg_ctx *ctx, const mg_model_batch *models, const mg_path_binding *bindings,
+                                uint32_t n_bindings, const uint32_t *lane_binding, const uint64_t *allowed,
+                                uint32_t first, uint32_t n, uint32_t *first_sat, uint64_t *sat_bits,
+                                float *kernel_ms) {
+    if (!ctx) return MG_EINVAL;
+    if (!ctx->have_lanes) return set_err(ctx, MG_ESTATE, "mg_explore_check before mg_lanes_alloc");
+    if (!ctx->S.node) return set_err(ctx, MG_ESTATE, "mg_explore_check needs symbolic planes (mg_sym_alloc)");
+    if (!ctx->E.path) return set_err(ctx, MG_ESTATE, "mg_explore_check needs explore planes (mg_explore_alloc)");
+    const uint32_t n_lanes = ctx->L.n;
+    if (first + (uint64_t)n > n_lanes)
+        return set_err(ctx, MG_EINVAL, "mg_explore_check: lanes [%u,%u) outside batch of %u", first, first + n, n_lanes);
+    BvState &bv = ctx->bv;
+    std::string msg;
+    if (models) {
+        int rc;
+        if ((rc = bv_models_check(models, msg)) || (rc = bv_tables_check(models, msg)))
+            return set_err(ctx, rc, "mg_explore_check: %s", msg.c_str());
+    } else if (bv.n_models == 0u) {
+        return set_err(ctx, MG_EINVAL, "mg_explore_check: no models (none given, none resident)");
+    }
+    const uint32_t n_models = models ? models->n_models : bv.n_models, n_vars = models ? models->n_vars : bv.n_vars;
+    const uint32_t n_tables = std::min<uint32_t>(models ? models->n_tables : bv.n_tables, MG_BV_TAB_INDEX_MASK + 1u);
+    if (n_bindings && !bindings) return set_err(ctx, MG_EINVAL, "mg_explore_check: bindings is null with n_bindings = %u", n_bindings);
+    for (uint32_t b = 0; b < n_bindings; ++b) {
+        const mg_path_binding &B = bindings[b];
+        bool ok = B.var_cdsize == MG_PATH_UNBOUND || B.var_cdsize < n_vars;
+        for (uint32_t k = 0; k < MG_ENV_WORDS; ++k) ok = ok && (B.var_env[k] == MG_PATH_UNBOUND || B.var_env[k] < n_vars);
+        if (!ok) return set_err(ctx, MG_EINVAL, "mg_explore_check: bindings[%u] names a variable past the pool's %u", b, n_vars);
+        if ((B.tab_calldata != MG_PATH_UNBOUND && B.tab_calldata >= n_tables) ||
+            (B.tab_storage != MG_PATH_UNBOUND && B.tab_storage >= n_tables))
+            return set_err(ctx, MG_EINVAL, "mg_explore_check: bindings[%u] names a table past the pool's %u", b, n_tables);
+    }
+    if (n == 0u) {
+        if (kernel_ms) *kernel_ms = 0.f;
+        return MG_OK;
+    }
+    if (!first_sat) return set_err(ctx, MG_EINVAL, "mg_explore_check: first_sat is null with n = %u", n);
+    if (!lane_binding) return set_err(ctx, MG_EINVAL, "mg_explore_check: lane_binding is null with n = %u", n);
+    for (uint32_t l = 0; l < n_lanes; ++l)
+        if (lane_binding[l] != MG_PATH_UNBOUND && lane_binding[l] >= n_bindings)
+            return set_err(ctx, MG_EINVAL, "mg_explore_check: lane_binding[%u] = %u with %u bindings", l, lane_binding[l],
+                           n_bindings);
+    // ---- everything is checked: from here on the call writes
+    HIPX(ctx, hipSetDevice(ctx->device));
+    int rc;
+    if (models) {
+        if ((rc = bv_models_alloc(bv, models, msg))) return set_err(ctx, rc, "mg_explore_check: %s", msg.c_str());
+        hipError_t e = bv_models_copy(bv, models, ctx->stream);
+        e = e ? e : hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) return set_err(ctx, MG_EDEVICE, "mg_explore_check: model upload: %s", hipGetErrorString(e));
+        bv_models_commit(bv, models);
+        bv.n_dags = 0;          // resident programs may name variables this pool lacks: mg_eval_run -> MG_ESTATE
+    }
+    const uint32_t bw = (n_models + 63u) / 64u;
+    // the largest arena among the checked lanes sizes the workspace
+    if ((rc = ensure_hxfer(ctx, (size_t)n * 4u))) return rc;
+    HIPX(ctx, hipMemcpyAsync(ctx->h_xfer, ctx->S.n_nodes + first, (size_t)n * 4u, hipMemcpyDeviceToHost, ctx->stream));
+    HIPX(ctx, hipStreamSynchronize(ctx->stream));
+    uint32_t ws_nodes = 1u;
+    {
+        const uint32_t *nn = reinterpret_cast<const uint32_t *>(ctx->h_xfer);
+        for (uint32_t i = 0; i < n; ++i)
+            if (nn[i] <= MG_PATH_MAX_NODES && nn[i] <= ctx->S.node_cap) ws_nodes = std::max(ws_nodes, nn[i]);
+    }
+    // work items (lane, group of chunks): enough groups to fill the GPU when n is small
+    const uint32_t groups_wanted = std::max<uint32_t>(1u, (PE_TARGET_WAVES + n - 1u) / n);
+    const uint32_t cpi = std::max<uint32_t>(1u, bw / std::min(groups_wanted, bw));
+    const uint32_t groups = (bw + cpi - 1u) / cpi;
+    const size_t ws_wave = (size_t)ws_nodes * 2u * PE_WAVE * sizeof(uint4);
+    const uint64_t items = (uint64_t)n * groups;
+    uint32_t waves = (uint32_t)std::min<uint64_t>(items, PE_MAX_WAVES);
+    waves = (uint32_t)std::max<uint64_t>(1u, std::min<uint64_t>(waves, PE_WS_LIMIT / ws_wave));
+    if ((rc = path_ensure(ctx, ctx->d_pws, ctx->pws_cap, ws_wave * waves, "workspace"))) return rc;
+    // the call's arrays, 16-byte aligned: inputs first (one H2D copy), then the results (one D2H copy)
+    auto up16 = [](size_t x) { return (x + 15u) & ~(size_t)15u; };
+    const size_t o_bind = 0, o_lb = up16(o_bind + (size_t)n_bindings * sizeof(mg_path_binding)),
+                 o_al = up16(o_lb + (size_t)n_lanes * 4u), in_bytes = up16(o_al + (allowed ? (size_t)n_bindings * bw * 8u : 0u)),
+                 o_fs = in_bytes, o_bits = up16(o_fs + (size_t)n * 4u),
+                 out_bytes = o_bits - o_fs + (sat_bits ? (size_t)n * bw * 8u : 0u);
+    if ((rc = path_ensure(ctx, ctx->d_pio, ctx->pio_cap, in_bytes + out_bytes, "arrays"))) return rc;
+    if ((rc = ensure_hxfer(ctx, std::max(in_bytes, out_bytes)))) return rc;
+    if (n_bindings) std::memcpy(ctx->h_xfer + o_bind, bindings, (size_t)n_bindings * sizeof(mg_path_binding));
+    std::memcpy(ctx->h_xfer + o_lb, lane_binding, (size_t)n_lanes * 4u);
+    if (allowed) std::memcpy(ctx->h_xfer + o_al, allowed, (size_t)n_bindings * bw * 8u);
+    HIPX(ctx, hipMemcpyAsync(ctx->d_pio, ctx->h_xfer, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIPX(ctx, hipMemsetAsync(ctx->d_pio + o_fs, 0xff, (size_t)n * 4u, ctx->stream));      // MG_BV_NO_MODEL
+    PathArgs P{};
+    P.path = ctx->E.path; P.path_len = ctx->E.path_len; P.root = ctx->E.root; P.path_cap = ctx->E.path_cap;
+    P.bind = reinterpret_cast<const mg_path_binding *>(ctx->d_pio + o_bind);
+    P.lane_binding = reinterpret_cast<const uint32_t *>(ctx->d_pio + o_lb);
+    P.allowed = allowed ? reinterpret_cast<const unsigned long long *>(ctx->d_pio + o_al) : nullptr;
+    P.n_bind = n_bindings; P.first = first; P.n = n; P.bit_words = bw; P.chunks_per_item = cpi; P.groups = groups;
+    P.values = bv.values; P.n_models = n_models;
+    P.tab = BvTables{bv.tab_start, bv.tab_count, bv.tab_entries, bv.tab_default};
+    P.ws = ctx->d_pws; P.ws_nodes = ws_nodes;
+    P.first_sat = reinterpret_cast<uint32_t *>(ctx->d_pio + o_fs);
+    P.sat_bits = sat_bits ? reinterpret_cast<unsigned long long *>(ctx->d_pio + o_bits) : nullptr;
+    HIPX(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    hipLaunchKernelGGL(k_path_check, dim3(waves), dim3(PE_WAVE), (size_t)((ws_nodes + 31u) / 32u) * 4u, ctx->stream,
+                       ctx->L, ctx->S, P);
+    HIPX(ctx, hipGetLastError());
+    HIPX(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+    HIPX(ctx, hipMemcpyAsync(ctx->h_xfer, ctx->d_pio + o_fs, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIPX(ctx, hipStreamSynchronize(ctx->stream));
+    std::memcpy(first_sat, ctx->h_xfer, (size_t)n * 4u);
+    if (sat_bits) std::memcpy(sat_bits, ctx->h_xfer + (o_bits - o_fs), (size_t)n * bw * 8u);
+    if (kernel_ms) HIPX(ctx, hipEventElapsedTime(kernel_ms, ctx->ev0, ctx->ev1));
     return MG_OK;
 }
 

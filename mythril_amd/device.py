@@ -239,6 +239,53 @@ class GpuDevice:
                                                  first, n), "mg_explore_download")
         return path, path_len, root
 
+    def explore_upload_paths(self, path, path_len, root, first: int = 0):
+        """mg_explore_upload: the inverse of explore_paths for lanes [first, first + n),
+        n = len(path_len); path uint32[n, path_cap]."""
+        path_len = np.ascontiguousarray(np.asarray(path_len, dtype=np.uint32).reshape(-1))
+        root = np.ascontiguousarray(np.asarray(root, dtype=np.uint32).reshape(-1))
+        n = path_len.size
+        path = np.ascontiguousarray(np.asarray(path, dtype=np.uint32))
+        if root.size != n or path.shape != (n, self.path_cap):
+            raise ValueError("explore_upload_paths: path is [n, path_cap], path_len and root are [n]")
+        self._check(self.lib.mg_explore_upload(self.ctx, path.ctypes.data, path_len.ctypes.data, root.ctypes.data,
+                                               first, n), "mg_explore_upload")
+
+    def explore_check(self, pool, bindings, lane_binding, allowed=None, first: int = 0, n: Optional[int] = None,
+                      bits: bool = False):
+        """mg_explore_check: which candidate model satisfies each lane's recorded path,
+        evaluated from the arenas on the device.  pool: a ModelPool, or None for the
+        one the last eval_upload left resident; bindings: native.MgPathBinding per
+        lineage; lane_binding: uint32[n_lanes], indexed by root[lane], an index into
+        bindings or MG_PATH_UNBOUND; allowed: uint64[len(bindings), ceil(n_models / 64)]
+        or None (every model).  Returns (first_sat uint32[n] -- a model index,
+        MG_BV_NO_MODEL or MG_PATH_UNKNOWN --, sat_bits uint64[n, words] or None,
+        kernel_ms)."""
+        n_lanes = self.shape.n
+        n = n_lanes - first if n is None else int(n)
+        bindings = list(bindings)
+        barr = (native.MgPathBinding * max(len(bindings), 1))(*bindings)
+        lb = np.ascontiguousarray(np.asarray(lane_binding, dtype=np.uint32).reshape(-1))
+        if lb.size != n_lanes:
+            raise ValueError("explore_check: lane_binding has one entry per lane of the batch")
+        mods = pool.c_struct() if pool is not None else None
+        n_models = pool.n_models if pool is not None else self._models.n_models
+        words = (n_models + 63) // 64
+        if allowed is not None:
+            allowed = np.ascontiguousarray(np.asarray(allowed, dtype=np.uint64))
+            if allowed.shape != (len(bindings), words):
+                raise ValueError("explore_check: allowed is [len(bindings), ceil(n_models / 64)]")
+        fs = np.zeros(max(n, 1), dtype=np.uint32)
+        sb = np.zeros((max(n, 1), words), dtype=np.uint64) if bits else None
+        ms = ctypes.c_float()
+        self._check(self.lib.mg_explore_check(
+            self.ctx, ctypes.byref(mods) if mods is not None else None, barr, len(bindings), lb.ctypes.data,
+            allowed.ctypes.data if allowed is not None else None, first, n, fs.ctypes.data,
+            sb.ctypes.data if bits else None, ctypes.byref(ms)), "mg_explore_check")
+        if mods is not None:
+            self._models = mods             # the resident pool now
+        return fs[:n], (sb[:n] if bits else None), ms.value
+
     def step(self, hook_mask=None, max_steps: int = 1 << 30, max_depth: int = 0,
              horizon: int = 0) -> StepStats:
         """mg_step (horizon 0) or mg_step_until: lanes also pause once their

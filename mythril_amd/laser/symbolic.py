@@ -841,6 +841,41 @@ def path_constraints(b, lane: int, state, path_row):
     return out
 
 
+def path_binding(state, var_names, tables):
+    """The mg_path_binding (native.MgPathBinding) of the lineage whose root lane
+    was packed from `state`, for a model pool with the variables `var_names` and
+    the tables `tables` (lower.TableSig, or anything with a .name): where the
+    device finds {id}_calldatasize, the {id}_calldata array, the five environment
+    words and the Storage{address} array when it evaluates the lineage's paths
+    (GpuDevice.explore_check).  The names are those of the state's own calldata,
+    environment and storage expressions; a word that is not a plain symbol (a
+    concrete value, a compound term) or that the pool does not carry stays
+    MG_PATH_UNBOUND, and a path that needs it is answered MG_PATH_UNKNOWN."""
+    from ..native import MgPathBinding
+    var_at = {name: i for i, name in enumerate(var_names)}
+    tab_at = {getattr(t, "name", t): i for i, t in enumerate(tables or [])}
+    out = MgPathBinding.unbound()
+
+    def symbol(x) -> Optional[str]:
+        raw = getattr(x, "raw", None)
+        return raw.param if raw is not None and raw.op == "var" and raw.width == 256 else None
+
+    def array(raw, rng: int) -> Optional[str]:
+        return raw.param[0] if raw is not None and raw.op == "array" and raw.param[1:] == (256, rng) else None
+
+    env = state.environment
+    cd = env.calldata
+    if is_symbolic_calldata(cd):
+        out.var_cdsize = var_at.get(symbol(cd.calldatasize), out.var_cdsize)
+        out.tab_calldata = tab_at.get(array(cd._calldata.raw, 8), out.tab_calldata)
+    for k, attr in _ENV_ATTR.items():
+        out.var_env[k] = var_at.get(symbol(getattr(env, attr)), out.var_env[k])
+    storage = env.active_account.storage
+    if not storage.concrete:
+        out.tab_storage = tab_at.get(array(storage.base_raw, 256), out.tab_storage)
+    return out
+
+
 def _fork_copy(state):
     """deepcopy(global_state) of the reference's fork (world state, machine
     state and account copies; expressions are immutable and shared)."""

@@ -121,6 +121,18 @@ class MgExploreStats(ctypes.Structure):
                 ("kernel_ms", ctypes.c_float), ("_padf", ctypes.c_float)]
 
 
+class MgPathBinding(ctypes.Structure):
+    """mg_path_binding: where one lineage's symbols live in the model batch
+    (abi.MG_PATH_UNBOUND: not bound)."""
+    _fields_ = [("var_cdsize", ctypes.c_uint32), ("tab_calldata", ctypes.c_uint32),
+                ("var_env", ctypes.c_uint32 * abi.MG_ENV_WORDS), ("tab_storage", ctypes.c_uint32)]
+
+    @classmethod
+    def unbound(cls) -> "MgPathBinding":
+        u = abi.MG_PATH_UNBOUND
+        return cls(u, u, (ctypes.c_uint32 * abi.MG_ENV_WORDS)(*[u] * abi.MG_ENV_WORDS), u)
+
+
 # every symbol include/mythgpu.h declares: name -> (restype, argtypes)
 _P, _U32, _U64, _I = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int
 _PU32 = ctypes.POINTER(ctypes.c_uint32)
@@ -149,6 +161,9 @@ SIGNATURES = {
     "mg_explore_alloc": (_I, [_P, _U32]),
     "mg_explore": (_I, [_P, _P, _U32, _U32, _U32, _P, _U32, ctypes.POINTER(MgExploreStats)]),
     "mg_explore_download": (_I, [_P, _P, _P, _P, _U32, _U32]),
+    "mg_explore_upload": (_I, [_P, _P, _P, _P, _U32, _U32]),
+    "mg_explore_check": (_I, [_P, ctypes.POINTER(MgModelBatch), _P, _U32, _P, _P, _U32, _U32, _P, _P,
+                              ctypes.POINTER(ctypes.c_float)]),
     "mg_step": (_I, [_P, _P, _U32, _U32, ctypes.POINTER(MgStepStats)]),
     "mg_step_async": (_I, [_P, _P, _U32, _U32]),
     "mg_run_batches": (_I, [_P, _P, _U32, _U32, _U32, ctypes.POINTER(MgStepStats)]),
