@@ -64,7 +64,8 @@ extern "C" {
                                   on a dispatcher entry, for active_function_name;
                                   additive: mg_eval_terms, mg_eval_min, mg_lanes_fork,
                                   mg_explore_alloc / mg_explore / mg_explore_download,
-                                  mg_explore_upload, mg_explore_check */
+                                  mg_explore_upload, mg_explore_check,
+                                  mg_explore_check_fn (mg_path_functions) */
 
 /* ------------------------------------------------------------------ errors */
 #define MG_OK          0
@@ -745,6 +746,67 @@ int         mg_explore_check(mg_ctx *ctx, const struct mg_model_batch *models,
                              uint32_t first, uint32_t n,
                              uint32_t *first_sat /* [n] */, uint64_t *sat_bits /* [n][ceil(n_models/64)] or NULL */,
                              float *kernel_ms);
+
+/* mg_explore_check with the models' uninterpreted functions bound: the tables of
+ * keccak256_<bits> and Power, which the pool carries as kernel 2 reads them (keys
+ * as smt/lower.py's TableSig.key_chunks makes them: one argument x of at most 512
+ * bits is (x mod 2^256, x >> 256), two arguments of at most 256 bits each are
+ * (first, second)).  Everything stated for mg_explore_check holds; mg_explore_check
+ * is this call with functions == NULL, and NULL is the same as a struct with
+ * nothing bound: MG_SYM_KECCAK and EXP's Power in a cone are then MG_PATH_UNKNOWN.
+ * The functions are the pool's, not a lineage's: one struct per call.
+ *
+ * Two more rules give values (each table read is part 0, and gives the table's
+ * default for that model when no entry matches):
+ *   MG_SYM_KECCAK(y, w)  node width 256; with x the input's value as a w-bit
+ *     integer, the table bound for width w at (x mod 2^256, x >> 256).  The input y
+ *     is a constant (w <= 256, masked to w), a node of width exactly w that the
+ *     rules above evaluate, or a tree of MG_SYM_CONCAT nodes: y high, z low, widths
+ *     w & 0xffff and w >> 16, each at least 1, their sum the node's width, which
+ *     inside such a tree may be 257..512; each operand is again a constant of at
+ *     most 256 bits, a node of exactly the stated width, or a CONCAT.  Any tree
+ *     shape is taken (sym_mem_ref's left-leaning chains, the host encoder's own), up
+ *     to MG_PATH_KECCAK_LEAVES leaves.
+ *   MG_SYM_BIN, w == 0x0a  node width 256: table tab_power at (value(y), value(z)),
+ *     y the base (first pop) and z the exponent, as symbolic.binary builds
+ *     Power(base, exponent).
+ * A lane is also MG_PATH_UNKNOWN when its cone holds an MG_SYM_KECCAK whose w is 0,
+ * above 512 or a width no table is bound for, whose node width is not 256, or whose
+ * input has more than MG_PATH_KECCAK_LEAVES leaves, a reference not below its
+ * referrer or past n_consts, or a node whose width is not the one its referrer
+ * states (w for y; a CONCAT's w for its operands); an input that is an
+ * MG_SYM_MLOADK (or holds any node the rules do not evaluate); Power with
+ * tab_power unbound.  A CONCAT wider than 256 bits has no value of its own: reached
+ * any other way than through a KECCAK input (a path condition, a BIN operand, an
+ * EXTRACT source, a chain tag) it makes the lane unknown, as in mg_explore_check.
+ *
+ * What stays with the caller, through `allowed`: the keccak conjunct (whichever
+ * registrations it covers), exponent_function_manager's side conditions and the
+ * result == Power(b, e) constraints of concrete EXP records.  The device evaluates
+ * the path's own entries and nothing else.
+ *
+ * Checked on the host with the rest (MG_EINVAL, nothing launched, nothing
+ * written): n_keccak above MG_PATH_KECCAK_WIDTHS; a bound width of 0 or above 512;
+ * a repeated width; tab_power or a keccak_tab entry that is neither below the
+ * pool's table count nor MG_PATH_UNBOUND.  Entries at and above n_keccak are not
+ * read.  The struct travels with the call's other arrays: the number of launches
+ * and copies is mg_explore_check's.                                              */
+#define MG_PATH_KECCAK_WIDTHS 8u      /* keccak256_<bits> tables one call binds */
+#define MG_PATH_KECCAK_LEAVES 64u     /* most leaves of a KECCAK input tree (a 512-bit input of whole bytes) */
+typedef struct mg_path_functions {    /* where the uninterpreted functions live in the model batch */
+    uint32_t tab_power;               /* Power (256, 256) -> 256: table index, or MG_PATH_UNBOUND */
+    uint32_t n_keccak;                /* <= MG_PATH_KECCAK_WIDTHS */
+    uint32_t keccak_bits[MG_PATH_KECCAK_WIDTHS];   /* input widths, 1..512, distinct */
+    uint32_t keccak_tab[MG_PATH_KECCAK_WIDTHS];    /* table of keccak256_<bits>, or MG_PATH_UNBOUND */
+} mg_path_functions;
+int         mg_explore_check_fn(mg_ctx *ctx, const struct mg_model_batch *models,
+                                const mg_path_binding *bindings, uint32_t n_bindings,
+                                const uint32_t *lane_binding /* [n_lanes], indexed by root[lane] */,
+                                const uint64_t *allowed /* [n_bindings][ceil(n_models/64)] or NULL */,
+                                const mg_path_functions *functions /* or NULL: nothing bound */,
+                                uint32_t first, uint32_t n,
+                                uint32_t *first_sat /* [n] */, uint64_t *sat_bits /* [n][ceil(n_models/64)] or NULL */,
+                                float *kernel_ms);
 
 /* Replaces the LaserEVM.exec() drain for device-eligible lanes (svm.py:293-337
  * + execute_state svm.py:369-491 + Instruction.evaluate instructions.py:235-267):

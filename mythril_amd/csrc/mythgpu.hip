@@ -1652,12 +1652,13 @@ static int path_ensure(mg_ctx *ctx, T *&p, size_t &cap, size_t bytes, const char
     return MG_OK;
 }
 
-// One D2H copy (the checked lanes' node counts), one H2D copy (the call's arrays),
-// one memset, one launch, one D2H copy (the results): none depends on n.
-extern "C" int mg_explore_check(mg_ctx *ctx, const mg_model_batch *models, const mg_path_binding *bindings,
-                                uint32_t n_bindings, const uint32_t *lane_binding, const uint64_t *allowed,
-                                uint32_t first, uint32_t n, uint32_t *first_sat, uint64_t *sat_bits,
-                                float *kernel_ms) {
+// One D2H copy (the checked lanes' node counts), one H2D copy (the call's arrays, the
+// function tables' struct among them), one memset, one launch, one D2H copy (the
+// results): none depends on n.
+extern "C" int mg_explore_check_fn(mg_ctx *ctx, const mg_model_batch *models, const mg_path_binding *bindings,
+                                   uint32_t n_bindings, const uint32_t *lane_binding, const uint64_t *allowed,
+                                   const mg_path_functions *functions, uint32_t first, uint32_t n,
+                                   uint32_t *first_sat, uint64_t *sat_bits, float *kernel_ms) {
     if (!ctx) return MG_EINVAL;
     if (!ctx->have_lanes) return set_err(ctx, MG_ESTATE, "mg_explore_check before mg_lanes_alloc");
     if (!ctx->S.node) return set_err(ctx, MG_ESTATE, "mg_explore_check needs symbolic planes (mg_sym_alloc)");
@@ -1685,6 +1686,31 @@ extern "C" int mg_explore_check(mg_ctx *ctx, const mg_model_batch *models, const
         if ((B.tab_calldata != MG_PATH_UNBOUND && B.tab_calldata >= n_tables) ||
             (B.tab_storage != MG_PATH_UNBOUND && B.tab_storage >= n_tables))
             return set_err(ctx, MG_EINVAL, "mg_explore_check: bindings[%u] names a table past the pool's %u", b, n_tables);
+    }
+    mg_path_functions fn;
+    std::memset(&fn, 0xff, sizeof fn);          // every field MG_PATH_UNBOUND
+    fn.n_keccak = 0u;
+    if (functions) {
+        if (functions->n_keccak > MG_PATH_KECCAK_WIDTHS)
+            return set_err(ctx, MG_EINVAL, "mg_explore_check: functions binds %u keccak widths, at most %u",
+                           functions->n_keccak, MG_PATH_KECCAK_WIDTHS);
+        if (functions->tab_power != MG_PATH_UNBOUND && functions->tab_power >= n_tables)
+            return set_err(ctx, MG_EINVAL, "mg_explore_check: functions names Power's table past the pool's %u", n_tables);
+        for (uint32_t j = 0; j < functions->n_keccak; ++j) {
+            const uint32_t bits = functions->keccak_bits[j], tab = functions->keccak_tab[j];
+            if (bits == 0u || bits > 512u)
+                return set_err(ctx, MG_EINVAL, "mg_explore_check: functions.keccak_bits[%u] = %u, not in 1..512", j, bits);
+            for (uint32_t i = 0; i < j; ++i)
+                if (functions->keccak_bits[i] == bits)
+                    return set_err(ctx, MG_EINVAL, "mg_explore_check: functions binds width %u twice", bits);
+            if (tab != MG_PATH_UNBOUND && tab >= n_tables)
+                return set_err(ctx, MG_EINVAL, "mg_explore_check: functions.keccak_tab[%u] names a table past the pool's %u",
+                               j, n_tables);
+            fn.keccak_bits[j] = bits;
+            fn.keccak_tab[j] = tab;
+        }
+        fn.tab_power = functions->tab_power;
+        fn.n_keccak = functions->n_keccak;
     }
     if (n == 0u) {
         if (kernel_ms) *kernel_ms = 0.f;
@@ -1730,7 +1756,8 @@ extern "C" int mg_explore_check(mg_ctx *ctx, const mg_model_batch *models, const
     // the call's arrays, 16-byte aligned: inputs first (one H2D copy), then the results (one D2H copy)
     auto up16 = [](size_t x) { return (x + 15u) & ~(size_t)15u; };
     const size_t o_bind = 0, o_lb = up16(o_bind + (size_t)n_bindings * sizeof(mg_path_binding)),
-                 o_al = up16(o_lb + (size_t)n_lanes * 4u), in_bytes = up16(o_al + (allowed ? (size_t)n_bindings * bw * 8u : 0u)),
+                 o_al = up16(o_lb + (size_t)n_lanes * 4u), o_fn = up16(o_al + (allowed ? (size_t)n_bindings * bw * 8u : 0u)),
+                 in_bytes = up16(o_fn + sizeof(mg_path_functions)),
                  o_fs = in_bytes, o_bits = up16(o_fs + (size_t)n * 4u),
                  out_bytes = o_bits - o_fs + (sat_bits ? (size_t)n * bw * 8u : 0u);
     if ((rc = path_ensure(ctx, ctx->d_pio, ctx->pio_cap, in_bytes + out_bytes, "arrays"))) return rc;
@@ -1738,6 +1765,7 @@ extern "C" int mg_explore_check(mg_ctx *ctx, const mg_model_batch *models, const
     if (n_bindings) std::memcpy(ctx->h_xfer + o_bind, bindings, (size_t)n_bindings * sizeof(mg_path_binding));
     std::memcpy(ctx->h_xfer + o_lb, lane_binding, (size_t)n_lanes * 4u);
     if (allowed) std::memcpy(ctx->h_xfer + o_al, allowed, (size_t)n_bindings * bw * 8u);
+    std::memcpy(ctx->h_xfer + o_fn, &fn, sizeof fn);
     HIPX(ctx, hipMemcpyAsync(ctx->d_pio, ctx->h_xfer, in_bytes, hipMemcpyHostToDevice, ctx->stream));
     HIPX(ctx, hipMemsetAsync(ctx->d_pio + o_fs, 0xff, (size_t)n * 4u, ctx->stream));      // MG_BV_NO_MODEL
     PathArgs P{};
@@ -1745,6 +1773,7 @@ extern "C" int mg_explore_check(mg_ctx *ctx, const mg_model_batch *models, const
     P.bind = reinterpret_cast<const mg_path_binding *>(ctx->d_pio + o_bind);
     P.lane_binding = reinterpret_cast<const uint32_t *>(ctx->d_pio + o_lb);
     P.allowed = allowed ? reinterpret_cast<const unsigned long long *>(ctx->d_pio + o_al) : nullptr;
+    P.fn = reinterpret_cast<const mg_path_functions *>(ctx->d_pio + o_fn);
     P.n_bind = n_bindings; P.first = first; P.n = n; P.bit_words = bw; P.chunks_per_item = cpi; P.groups = groups;
     P.values = bv.values; P.n_models = n_models;
     P.tab = BvTables{bv.tab_start, bv.tab_count, bv.tab_entries, bv.tab_default};
@@ -1762,6 +1791,14 @@ extern "C" int mg_explore_check(mg_ctx *ctx, const mg_model_batch *models, const
     if (sat_bits) std::memcpy(sat_bits, ctx->h_xfer + (o_bits - o_fs), (size_t)n * bw * 8u);
     if (kernel_ms) HIPX(ctx, hipEventElapsedTime(kernel_ms, ctx->ev0, ctx->ev1));
     return MG_OK;
+}
+
+extern "C" int mg_explore_check(mg_ctx *ctx, const mg_model_batch *models, const mg_path_binding *bindings,
+                                uint32_t n_bindings, const uint32_t *lane_binding, const uint64_t *allowed,
+                                uint32_t first, uint32_t n, uint32_t *first_sat, uint64_t *sat_bits,
+                                float *kernel_ms) {
+    return mg_explore_check_fn(ctx, models, bindings, n_bindings, lane_binding, allowed, nullptr, first, n, first_sat,
+                               sat_bits, kernel_ms);
 }
 
 // Whole batches back to back on the stream: each batch re-initialises every

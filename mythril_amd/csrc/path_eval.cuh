@@ -14,11 +14,18 @@
 //               refers only to nodes below it): marks what the path needs in an LDS
 //               bitmap and decides MG_PATH_UNKNOWN.  Every index followed later is
 //               checked here, against the lane's own counts and the planes'
-//               capacities; an unknown lane is never evaluated.
+//               capacities; an unknown lane is never evaluated.  A KECCAK node's
+//               input may be a tree of CONCAT nodes wider than 256 bits: the tree is
+//               walked from the KECCAK node with a stack in LDS, its leaves (256 bits
+//               at most) are marked, and the wide nodes themselves never are -- a
+//               wide node marked any other way makes the lane unknown.
 //   evaluation  marked nodes in ascending order; a node's value goes to the wave's
 //               workspace slice [node][half][64 threads] as two uint4 per thread (a
 //               dynamically indexed per-thread array would live in scratch) and is
-//               read back by the same thread only.
+//               read back by the same thread only.  A KECCAK node walks its tree
+//               again, low part first, and assembles the table key (k0, k1) from the
+//               leaves' values with shifts by wave-uniform amounts; wide nodes have no
+//               workspace slot.
 //   result      __ballot of "every entry holds", and-ed with the lineage's allowed
 //               word; thread 0 writes the sat_bits word and the first model.
 //
@@ -34,6 +41,7 @@
 #define PE_TARGET_WAVES 2048u               // waves wanted per launch (8 per CU)
 #define PE_MAX_WAVES 4096u
 #define PE_WS_LIMIT (1ull << 30)            // workspace bytes one call may ask for
+#define PE_MAX_LEAVES MG_PATH_KECCAK_LEAVES // leaves of a KECCAK input tree (= the walk's stack)
 
 struct PathArgs {
     // the explore planes
@@ -43,6 +51,7 @@ struct PathArgs {
     const mg_path_binding *bind;            // [n_bind]
     const uint32_t *lane_binding;           // [L.n]
     const unsigned long long *allowed;      // [n_bind][bit_words] or null
+    const mg_path_functions *fn;            // the bound function tables (everything unbound: none)
     uint32_t n_bind, first, n, bit_words, chunks_per_item, groups;
     // the model pool (BvState)
     const uint4 *values;
@@ -72,6 +81,8 @@ struct PeLane {
     const uint4 *storage;                   // L.storage + 4 l, row pitch 4 N
     uint32_t var_cdsize, tab_calldata, tab_storage;
     const uint32_t *var_env;                // the binding's five words
+    const mg_path_functions *fn;
+    uint2 *stk;                             // LDS [PE_MAX_LEAVES]: the tree walk's (ref, width)
 };
 
 DEV bool pe_marked(const uint32_t *marks, uint32_t k) { return (uni(marks[k >> 5]) >> (k & 31u)) & 1u; }
@@ -83,6 +94,60 @@ DEV bool pe_ref(const PeLane &A, uint32_t *marks, uint32_t k, uint32_t r) {
     if (r & MG_SYM_CONST) return (r & ~MG_SYM_CONST) < A.nc;
     if (r >= k) return false;
     pe_mark(marks, r);
+    return true;
+}
+
+// The table bound for keccak256_<bits>, by scalar comparison with the bound widths.
+DEV uint32_t pe_keccak_tab(const PeLane &A, uint32_t bits) {
+    uint32_t tab = MG_PATH_UNBOUND;
+    const uint32_t nk = min(uni(A.fn->n_keccak), MG_PATH_KECCAK_WIDTHS);
+    for (uint32_t j = 0; j < nk; ++j)
+        if (uni(A.fn->keccak_bits[j]) == bits) tab = uni(A.fn->keccak_tab[j]);
+    return tab;
+}
+
+// The tree walk's stack: every thread writes the one value, the read is a scalar.
+DEV void pe_push(uint2 *stk, uint32_t sp, uint32_t r, uint32_t width) { stk[sp] = make_uint2(r, width); }
+DEV void pe_pop(const uint2 *stk, uint32_t sp, uint32_t &r, uint32_t &width) {
+    const uint2 e = stk[sp];
+    r = uni(e.x); width = uni(e.y);
+}
+
+// A reference of `width` bits inside a KECCAK input, made by node `parent`: a
+// constant below the lane's count (256 bits at most) or a node below the parent.
+DEV bool pe_tree_ref(const PeLane &A, uint32_t parent, uint32_t r, uint32_t width) {
+    if (width == 0u || width > 512u) return false;
+    if (r & MG_SYM_CONST) return width <= 256u && (r & ~MG_SYM_CONST) < A.nc;
+    return r < parent;
+}
+
+// The cone pass of KECCAK node k's input (y, bits): every reference of the tree is
+// below its referrer, every width is the one its referrer states, the tree has at
+// most PE_MAX_LEAVES leaves; the leaves that are nodes are marked.  With
+// leaves + sp <= PE_MAX_LEAVES throughout, the stack never outgrows its array.
+DEV bool pe_cone_keccak(const PeLane &A, uint32_t *marks, uint32_t k, uint32_t y, uint32_t bits) {
+    if (!pe_tree_ref(A, k, y, bits)) return false;
+    uint32_t sp = 0u, leaves = 0u;
+    pe_push(A.stk, sp++, y, bits);
+    while (sp) {
+        uint32_t r, ew;
+        pe_pop(A.stk, --sp, r, ew);
+        if (r & MG_SYM_CONST) { ++leaves; continue; }
+        const uint4 nd = A.node[(size_t)r * A.N];
+        const uint32_t kind = uni(nd.x) & 0xffu, width = uni(nd.x) >> 8, ny = uni(nd.y), nz = uni(nd.z), w = uni(nd.w);
+        if (width != ew) return false;
+        if (kind == MG_SYM_CONCAT && width > 256u) {
+            const uint32_t wy = w & 0xffffu, wz = w >> 16;
+            if (wy + wz != width || !pe_tree_ref(A, r, ny, wy) || !pe_tree_ref(A, r, nz, wz)) return false;
+            if (leaves + sp + 2u > PE_MAX_LEAVES) return false;
+            pe_push(A.stk, sp++, ny, wy);
+            pe_push(A.stk, sp++, nz, wz);
+            continue;
+        }
+        if (width > 256u) return false;
+        pe_mark(marks, r);
+        ++leaves;
+    }
     return true;
 }
 
@@ -99,7 +164,9 @@ DEV bool pe_cone_node(const PeLane &A, uint32_t *marks, uint32_t k) {
     case MG_SYM_CDBYTE: return width == 8u && cd;
     case MG_SYM_CDBYTEX: return width == 8u && cd && pe_ref(A, marks, k, y);
     case MG_SYM_BIN: {
-        if (w >= 32u || !((PE_BIN_OPS >> w) & 1u)) return false;
+        if (w == 0x0au) {                                   // EXP: Power(base y, exponent z)
+            if (width != 256u || uni(A.fn->tab_power) == MG_PATH_UNBOUND) return false;
+        } else if (w >= 32u || !((PE_BIN_OPS >> w) & 1u)) return false;
         if (!pe_ref(A, marks, k, y) || !pe_ref(A, marks, k, z)) return false;
         if (w == 0x1au) {                                   // BYTE: a constant index below 32
             if (!(y & MG_SYM_CONST)) return false;
@@ -133,7 +200,10 @@ DEV bool pe_cone_node(const PeLane &A, uint32_t *marks, uint32_t k) {
         }
         return true;
     }
-    default: return false;          // KECCAK, TERM, MLOADK, MSTOREK, BALANCE, anything else
+    case MG_SYM_KECCAK:
+        return width == 256u && w >= 1u && w <= 512u && pe_keccak_tab(A, w) != MG_PATH_UNBOUND &&
+               pe_cone_keccak(A, marks, k, y, w);
+    default: return false;          // TERM, MLOADK, MSTOREK, BALANCE, anything else
     }
 }
 
@@ -156,6 +226,37 @@ DEV U256 pe_fetch(const PeLane &A, const uint4 *ws, uint32_t r) {
 DEV U256 pe_var(const BvCtx &c, uint32_t var) {
     return ld2(reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(c.values) +
                                                (var * c.n_models + c.model()) * 32u));
+}
+
+// The key (k0, k1) of KECCAK input (y, bits) under this thread's model: the leaves'
+// values, low part first, each at its wave-uniform bit position; a part across bit
+// 256 leaves its low bits in k0 and its high bits in k1.  The cone pass accepted the
+// tree, so nothing is checked again.
+DEV void pe_keccak_key(const PeLane &A, const uint4 *ws, uint32_t y, uint32_t bits, U256 &k0, U256 &k1) {
+    k0 = u_zero(); k1 = u_zero();
+    uint32_t sp = 0u, pos = 0u;
+    pe_push(A.stk, sp++, y, bits);
+    while (sp) {
+        uint32_t r, ew;
+        pe_pop(A.stk, --sp, r, ew);
+        if (!(r & MG_SYM_CONST)) {
+            const uint4 nd = A.node[(size_t)r * A.N];
+            if ((uni(nd.x) & 0xffu) == MG_SYM_CONCAT && (uni(nd.x) >> 8) > 256u) {
+                const uint32_t w = uni(nd.w);
+                pe_push(A.stk, sp++, uni(nd.y), w & 0xffffu);           // high part: after the low one
+                pe_push(A.stk, sp++, uni(nd.z), w >> 16);
+                continue;
+            }
+        }
+        const U256 v = bv_mask(pe_fetch(A, ws, r), ew);
+        if (pos < 256u) {
+            k0 = u_or(k0, u_shl_u(v, pos));
+            if (pos + ew > 256u) k1 = u_or(k1, u_shr_u(v, 256u - pos, 0u));
+        } else {
+            k1 = u_or(k1, u_shl_u(v, pos - 256u));
+        }
+        pos += ew;
+    }
 }
 
 // The value of node k under this thread's model (the cone pass accepted the node).
@@ -189,6 +290,7 @@ DEV U256 pe_eval_node(const PeLane &A, const BvCtx &c, const uint4 *ws, uint32_t
         case 0x03: r = u_sub(a, b); break;
         case 0x04: case 0x06: r = bv_udivrem(w == 0x04u, a, b); break;                        // bvudiv, bvurem
         case 0x05: case 0x07: r = bv_divop(w == 0x05u ? MG_BV_SDIV : MG_BV_SREM, 256u, 0u, a, b); break;
+        case 0x0a: r = bv_table(c, a, b, uni(A.fn->tab_power)); break;                         // Power(base y, exponent z)
         case 0x10: r = u_small(u_lt(a, b)); break;
         case 0x11: r = u_small(u_lt(b, a)); break;
         case 0x12: r = u_small(u_slt(a, b)); break;
@@ -213,6 +315,12 @@ DEV U256 pe_eval_node(const PeLane &A, const BvCtx &c, const uint4 *ws, uint32_t
     case MG_SYM_CONCAT: {
         const uint32_t wy = w & 0xffffu, wz = w >> 16;
         r = u_or(u_shl_u(bv_mask(pe_fetch(A, ws, y), wy), wz), bv_mask(pe_fetch(A, ws, z), wz));
+        break;
+    }
+    case MG_SYM_KECCAK: {
+        U256 k0, k1;
+        pe_keccak_key(A, ws, y, w, k0, k1);
+        r = bv_table(c, k0, k1, pe_keccak_tab(A, w));
         break;
     }
     default: {                                                                                // MG_SYM_SLOAD
@@ -240,6 +348,7 @@ DEV U256 pe_eval_node(const PeLane &A, const BvCtx &c, const uint4 *ws, uint32_t
 
 __global__ __launch_bounds__(PE_WAVE) void k_path_check(DevLanes L, DevSym S, PathArgs P) {
     extern __shared__ uint32_t pe_marks[];                  // one bit per node of the lane
+    __shared__ uint2 pe_stack[PE_MAX_LEAVES];               // the walk of a KECCAK input tree
     const uint32_t t = __lane_id();
     const uint32_t N = L.N;
     uint4 *const ws = P.ws + (size_t)blockIdx.x * P.ws_nodes * 2u * PE_WAVE + t;
@@ -265,6 +374,7 @@ __global__ __launch_bounds__(PE_WAVE) void k_path_check(DevLanes L, DevSym S, Pa
         known = known && b < P.n_bind;
         A.var_cdsize = A.tab_calldata = A.tab_storage = MG_PATH_UNBOUND;
         A.var_env = nullptr;
+        A.fn = P.fn; A.stk = pe_stack;
         if (known) {
             const mg_path_binding *B = P.bind + b;
             A.var_cdsize = uni(B->var_cdsize); A.tab_calldata = uni(B->tab_calldata);

@@ -252,13 +252,16 @@ class GpuDevice:
                                                first, n), "mg_explore_upload")
 
     def explore_check(self, pool, bindings, lane_binding, allowed=None, first: int = 0, n: Optional[int] = None,
-                      bits: bool = False):
+                      bits: bool = False, functions=None):
         """mg_explore_check: which candidate model satisfies each lane's recorded path,
         evaluated from the arenas on the device.  pool: a ModelPool, or None for the
         one the last eval_upload left resident; bindings: native.MgPathBinding per
         lineage; lane_binding: uint32[n_lanes], indexed by root[lane], an index into
         bindings or MG_PATH_UNBOUND; allowed: uint64[len(bindings), ceil(n_models / 64)]
-        or None (every model).  Returns (first_sat uint32[n] -- a model index,
+        or None (every model); functions: a native.MgPathFunctions
+        (symbolic.path_functions) naming the pool's Power and keccak256_<bits> tables
+        (mg_explore_check_fn), or None: mg_explore_check, under which a KECCAK or Power
+        node makes its lane unknown.  Returns (first_sat uint32[n] -- a model index,
         MG_BV_NO_MODEL or MG_PATH_UNKNOWN --, sat_bits uint64[n, words] or None,
         kernel_ms)."""
         n_lanes = self.shape.n
@@ -278,10 +281,13 @@ class GpuDevice:
         fs = np.zeros(max(n, 1), dtype=np.uint32)
         sb = np.zeros((max(n, 1), words), dtype=np.uint64) if bits else None
         ms = ctypes.c_float()
-        self._check(self.lib.mg_explore_check(
-            self.ctx, ctypes.byref(mods) if mods is not None else None, barr, len(bindings), lb.ctypes.data,
-            allowed.ctypes.data if allowed is not None else None, first, n, fs.ctypes.data,
-            sb.ctypes.data if bits else None, ctypes.byref(ms)), "mg_explore_check")
+        head = (self.ctx, ctypes.byref(mods) if mods is not None else None, barr, len(bindings), lb.ctypes.data,
+                allowed.ctypes.data if allowed is not None else None)
+        tail = (first, n, fs.ctypes.data, sb.ctypes.data if bits else None, ctypes.byref(ms))
+        if functions is None:
+            self._check(self.lib.mg_explore_check(*head, *tail), "mg_explore_check")
+        else:
+            self._check(self.lib.mg_explore_check_fn(*head, ctypes.byref(functions), *tail), "mg_explore_check_fn")
         if mods is not None:
             self._models = mods             # the resident pool now
         return fs[:n], (sb[:n] if bits else None), ms.value

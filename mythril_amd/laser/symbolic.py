@@ -876,6 +876,31 @@ def path_binding(state, var_names, tables):
     return out
 
 
+def path_functions(tables):
+    """The mg_path_functions (native.MgPathFunctions) of a model pool with the tables
+    `tables` (lower.TableSig): Power (256, 256) -> 256 and every keccak256_<bits>
+    (bits) -> 256 with bits <= 512, the first MG_PATH_KECCAK_WIDTHS of them in
+    ascending width.  A pool without a function leaves it unbound, and a path that
+    needs it is answered MG_PATH_UNKNOWN (GpuDevice.explore_check, functions=)."""
+    from ..native import MgPathFunctions
+    from ..abi import MG_PATH_KECCAK_WIDTHS
+    out = MgPathFunctions.unbound()
+    keccak = {}
+    for i, t in enumerate(tables or []):
+        if getattr(t, "kind", None) != "uf":
+            continue
+        if t.name == "Power" and t.domain == (256, 256) and t.range == 256:
+            out.tab_power = i
+        elif t.name.startswith("keccak256_") and t.name[10:].isdigit() and t.range == 256:
+            bits = int(t.name[10:])
+            if t.domain == (bits,) and 1 <= bits <= 512:
+                keccak.setdefault(bits, i)
+    for j, bits in enumerate(sorted(keccak)[:MG_PATH_KECCAK_WIDTHS]):
+        out.keccak_bits[j], out.keccak_tab[j] = bits, keccak[bits]
+        out.n_keccak = j + 1
+    return out
+
+
 def _fork_copy(state):
     """deepcopy(global_state) of the reference's fork (world state, machine
     state and account copies; expressions are immutable and shared)."""

@@ -133,6 +133,19 @@ class MgPathBinding(ctypes.Structure):
         return cls(u, u, (ctypes.c_uint32 * abi.MG_ENV_WORDS)(*[u] * abi.MG_ENV_WORDS), u)
 
 
+class MgPathFunctions(ctypes.Structure):
+    """mg_path_functions: where the pool's Power and keccak256_<bits> tables live
+    (mg_explore_check_fn; abi.MG_PATH_UNBOUND: not bound)."""
+    _fields_ = [("tab_power", ctypes.c_uint32), ("n_keccak", ctypes.c_uint32),
+                ("keccak_bits", ctypes.c_uint32 * abi.MG_PATH_KECCAK_WIDTHS),
+                ("keccak_tab", ctypes.c_uint32 * abi.MG_PATH_KECCAK_WIDTHS)]
+
+    @classmethod
+    def unbound(cls) -> "MgPathFunctions":
+        u, k = abi.MG_PATH_UNBOUND, abi.MG_PATH_KECCAK_WIDTHS
+        return cls(u, 0, (ctypes.c_uint32 * k)(*[0] * k), (ctypes.c_uint32 * k)(*[u] * k))
+
+
 # every symbol include/mythgpu.h declares: name -> (restype, argtypes)
 _P, _U32, _U64, _I = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int
 _PU32 = ctypes.POINTER(ctypes.c_uint32)
@@ -164,7 +177,9 @@ SIGNATURES = {
     "mg_explore_upload": (_I, [_P, _P, _P, _P, _U32, _U32]),
     "mg_explore_check": (_I, [_P, ctypes.POINTER(MgModelBatch), _P, _U32, _P, _P, _U32, _U32, _P, _P,
                               ctypes.POINTER(ctypes.c_float)]),
-    "mg_step": (_I, [_P, _P, _U32, _U32, ctypes.POINTER(MgStepStats)]),
+    "mg_explore_check_fn": (_I, [_P, ctypes.POINTER(MgModelBatch), _P, _U32, _P, _P, ctypes.POINTER(MgPathFunctions),
+                                 _U32, _U32, _P, _P, ctypes.POINTER(ctypes.c_float)]),
+    "mg_step":(_I, [_P, _P, _U32, _U32, ctypes.POINTER(MgStepStats)]),
     "mg_step_async": (_I, [_P, _P, _U32, _U32]),
     "mg_run_batches": (_I, [_P, _P, _U32, _U32, _U32, ctypes.POINTER(MgStepStats)]),
     "mg_step_until": (_I, [_P, _P, _U32, _U32, _U32, ctypes.POINTER(MgStepStats)]),
@@ -216,7 +231,11 @@ def load() -> ctypes.CDLL:
                 "rebuild with `python -c 'import __graft_entry__ as g; g.build()'`")
     lib = ctypes.CDLL(str(path))
     for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)
+        fn = getattr(lib, name, None)
+        if fn is None:
+            if "MYTHGPU_LIB" in os.environ:                 # an A/B variant built before the call existed
+                continue
+            raise MythGpuError(f"{path} does not export {name}")
         fn.restype = res
         fn.argtypes = args
     _lib = lib
