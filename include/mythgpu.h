@@ -660,6 +660,77 @@ int         mg_explore_download(mg_ctx *ctx, uint32_t *path /* [n][path_cap] */,
 int         mg_explore_upload(mg_ctx *ctx, const uint32_t *path /* [n][path_cap] */,
                               const uint32_t *path_len /* [n] */, const uint32_t *root /* [n] */,
                               uint32_t first, uint32_t n);
+/* mg_explore with the paths kept: the same arguments, plan, rounds, statistics and
+ * host-side checks, but root, path_len and path stay as the last mg_explore,
+ * mg_explore_resume or mg_explore_upload left them; only the free marks are cleared
+ * and set again from this call's list.  A lane handed out from the list takes its
+ * source's root and path, as any free lane does, whatever path it held before.  A
+ * lane that is MG_FORK when the call starts (a starved one) is planned in the
+ * first round.  With mg_harvest_select / mg_harvest_download below this is the
+ * loop "explore, take out what finished, put those lanes into the free list,
+ * explore again" with no path lost and no whole-batch download.               */
+int         mg_explore_resume(mg_ctx *ctx, const uint64_t hook_mask[4], uint32_t max_steps,
+                              uint32_t max_depth, uint32_t max_rounds, const uint32_t *free_lanes,
+                              uint32_t n_free, mg_explore_stats *stats);
+
+/* Finished lanes, chosen where the statuses are and fetched in one transfer.
+ *
+ * mg_harvest_select.  Lane l < n_lanes matches when status[l] < 32, bit status[l]
+ * of status_mask is set and l is not in skip (a lane that was never uploaded holds
+ * 0xffffffff and never matches).  skip is the caller's free list -- the lanes whose
+ * contents it has already taken or never filled --, strictly ascending, every
+ * entry below n_lanes.  The matching lanes are ranked in ascending lane order and
+ * the first min(matched, max_lanes) are selected (max_lanes above n_lanes is
+ * clipped); their indices stay on the device as an ascending list.  info: n,
+ * matched, and the largest sp, msize, storage_count, trace_len, rec_len, n_nodes,
+ * n_consts and path_len among the SELECTED lanes (0 when none is selected or the
+ * batch has no such plane: trace_cap / rec_cap of 0, no symbolic planes, no explore
+ * planes); kernel_ms from the first kernel to the last.  status_mask == 0 and
+ * max_lanes == 0 are valid and select nothing.  The call uploads nothing but skip,
+ * reads one small block back under one stream synchronisation, and its numbers of
+ * launches and copies depend on none of n_lanes, matched and n; it writes nothing
+ * of the lane image.  MG_HARVEST_BLOCKS (1..1024, default 1024, read per call) caps
+ * the number of blocks that scan the statuses.
+ * Checked on the host before any launch: MG_ESTATE without a batch or an upload;
+ * MG_EINVAL for a NULL info, a NULL skip with n_skip > 0, or a skip that is not
+ * strictly ascending with every entry below n_lanes (the message names the index).
+ *
+ * mg_harvest_download.  Row i of every host array is device lane lanes[i] of the
+ * last mg_harvest_select (host->n and, when given, sym->n must equal its info.n).
+ * The scalars, fent (when host->fent is given), calldata and the environment words
+ * go whole, as in mg_lanes_download; rows go below the selection's largest count:
+ * stack and stag below info.sp, memory and mtag below info.msize, storage and
+ * sttag below info.storage_count, trace / records below info.trace_len /
+ * info.rec_len (trace_len / rec_len themselves when the host's trace_cap / rec_cap
+ * is not 0), arena nodes below info.n_nodes, constants below info.n_consts; every
+ * bound is clipped to the host image's capacity, which may be below the batch's,
+ * and host cells at and above a bound keep their contents.  A NULL pointer in host
+ * skips that field.  sym may be NULL; path, path_len and root are all NULL or all
+ * given; path is [n][path_cap] as in mg_explore_download, entries at and above a
+ * lane's path_len are 0.  Taint planes are not part of the call.  Everything
+ * crosses PCIe in one copy under one stream synchronisation, whatever n is.
+ * The selection is dropped by mg_lanes_alloc, mg_sym_alloc and mg_explore_alloc;
+ * without one (also before the first select) the call answers MG_ESTATE.  It is
+ * not dropped by a step: a download after the image was stepped returns the
+ * current image of the listed lanes under the select-time bounds, and still reads
+ * inside the planes because every bound is at most a capacity.  MG_EINVAL, with
+ * nothing written: host->n (or sym->n) != info.n, capacities above the batch's,
+ * path without explore planes, sym without symbolic planes, path / path_len / root
+ * not given together.  After a selection of n == 0 the call succeeds and does
+ * nothing.                                                                       */
+typedef struct mg_harvest_info {
+    uint32_t n;        /* lanes selected, <= max_lanes                                   */
+    uint32_t matched;  /* lanes that matched; matched - n are left (the lowest lanes win) */
+    uint32_t sp, msize, storage_count, trace_len, rec_len,   /* largest count among the  */
+             n_nodes, n_consts, path_len;                    /* SELECTED lanes (0 if none
+                                                                or the plane is absent)  */
+    float    kernel_ms; uint32_t _pad;
+} mg_harvest_info;
+int         mg_harvest_select(mg_ctx *ctx, uint32_t status_mask, const uint32_t *skip, uint32_t n_skip,
+                              uint32_t max_lanes, mg_harvest_info *info);
+int         mg_harvest_download(mg_ctx *ctx, uint32_t *lanes /* [n] */, mg_lane_soa *host /* host->n == n */,
+                                mg_sym_soa *sym /* or NULL */, uint32_t *path /* [n][path_cap] or NULL */,
+                                uint32_t *path_len, uint32_t *root /* both NULL iff path is NULL */);
 
 /* The fork filter's question, "does any cached model satisfy this lane's path"
  * (svm.py:319-326 -> ModelCache.check_quick_sat, support_utils.py:60-68), answered

@@ -1,0 +1,146 @@
+// lane_harvest.cuh — mg_harvest_select / mg_harvest_download: the finished lanes of
+// a batch chosen where the statuses are, and their rows gathered through a lane
+// list (include/mythgpu.h states the contract).
+//
+// The selection is lane_explore.cuh's plan pattern restated for one class (that
+// file's kernels are left as they are; nothing is shared with them):
+//
+//   k_harvest_mark    one thread per skip entry: skipm[skip[j]] = 1 (skipm was cleared).
+//   k_harvest_scan    block b owns the lanes [b * chunk, (b + 1) * chunk), chunk a
+//                     multiple of 256, so there are at most HV_MAX_BLOCKS block totals
+//                     whatever n is.  A lane matches when its status is below 32, that
+//                     bit of the mask is set and it is not marked.  The matching lanes
+//                     are ranked in ascending lane order: a __ballot / popcount rank
+//                     inside each wave64, the four wave totals of a block through LDS,
+//                     a running carry over the block's tiles.
+//   k_harvest_totals  one block.  Exclusive scan of the block totals; n and matched;
+//                     the eight maxima zeroed for the emit kernel.
+//   k_harvest_emit    one thread per lane.  A matching lane of global rank r < max_lanes
+//                     is selected: list[r] = lane.  The maxima of the eight counts are
+//                     taken over the selected lanes only: a wave reduction, then at most
+//                     one atomicMax per wave and field.
+//
+// No block waits for another: the kernels are ordered by the stream.  None of them
+// writes the lane image.
+//
+// The gather kernels are mythgpu.hip's k_xfer_gather with the device lane taken
+// from the list.  Invariant they rely on: every entry list[0 .. n) was written by
+// k_harvest_emit from a thread whose lane index it is, so it is below n_lanes; the
+// host never passes a count above the n that k_harvest_totals reported, and the
+// list lives as long as the planes it indexes (mg_lanes_alloc, mg_sym_alloc and
+// mg_explore_alloc drop the selection).
+#pragma once
+
+#define HV_MAX_BLOCKS 1024u
+#define HV_NONE 0xffffffffu     // rank of a lane that does not match
+#define HV_FIELDS 8u            // sp, msize, storage_count, trace_len, rec_len, n_nodes, n_consts, path_len
+
+struct DevHarvest {
+    uint32_t *skipm;    // [N] 1: the lane is in the call's skip list
+    uint32_t *skip;     // [N] the call's skip list
+    uint32_t *rank;     // [N] block-local rank among the matching lanes, or HV_NONE
+    uint32_t *list;     // [N] the selection, ascending
+    uint32_t *bt;       // [HV_MAX_BLOCKS] block totals
+    uint32_t *boff;     // [HV_MAX_BLOCKS] exclusive block offsets
+    uint32_t *info;     // [2 + HV_FIELDS] n, matched, the maxima (mg_harvest_info's first words)
+};
+
+// the per-lane counts the maxima are taken of; a null pointer is an absent plane
+struct HarvestCounts {
+    const uint32_t *f[HV_FIELDS];
+};
+
+__global__ __launch_bounds__(256) void k_harvest_mark(DevHarvest H, uint32_t n_skip) {
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < n_skip) H.skipm[H.skip[j]] = 1u;     // the host checked every entry against n_lanes
+}
+
+__global__ __launch_bounds__(256) void k_harvest_scan(DevHarvest H, const uint32_t *__restrict__ status, uint32_t n,
+                                                      uint32_t mask, uint32_t chunk) {
+    __shared__ uint32_t sh[4];
+    const uint32_t x = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    const unsigned long long below = (1ull << x) - 1ull;
+    const uint32_t lo = blockIdx.x * chunk;
+    uint32_t carry = 0u;                                     // the block's carry over its tiles
+    for (uint32_t t = 0; t < chunk; t += 256u) {
+        const uint32_t l = lo + t + threadIdx.x;
+        bool match = false;
+        if (l < n) {
+            const uint32_t st = status[l];
+            match = st < 32u && (mask >> st & 1u) && !H.skipm[l];
+        }
+        const unsigned long long b = __ballot(match);
+        if (x == 0u) sh[w] = (uint32_t)__popcll(b);
+        __syncthreads();
+        uint32_t p = 0u, tot = 0u;
+#pragma unroll
+        for (uint32_t k = 0; k < 4u; ++k) {
+            if (k < w) p += sh[k];
+            tot += sh[k];
+        }
+        if (l < n) H.rank[l] = match ? carry + p + (uint32_t)__popcll(b & below) : HV_NONE;
+        carry += tot;
+        __syncthreads();                                     // sh is rewritten by the next tile
+    }
+    if (threadIdx.x == 0u) H.bt[blockIdx.x] = carry;
+}
+
+// one block of HV_MAX_BLOCKS threads: nb <= HV_MAX_BLOCKS block totals
+__global__ __launch_bounds__(1024) void k_harvest_totals(DevHarvest H, uint32_t nb, uint32_t max_lanes) {
+    __shared__ uint32_t s[2][HV_MAX_BLOCKS];
+    const uint32_t t = threadIdx.x;
+    const uint32_t v = t < nb ? H.bt[t] : 0u;
+    s[0][t] = v;
+    __syncthreads();
+    uint32_t cur = 0u;
+    for (uint32_t d = 1u; d < HV_MAX_BLOCKS; d <<= 1) {      // inclusive scan, double-buffered
+        s[cur ^ 1u][t] = s[cur][t] + (t >= d ? s[cur][t - d] : 0u);
+        cur ^= 1u;
+        __syncthreads();
+    }
+    if (t < nb) H.boff[t] = s[cur][t] - v;
+    if (t == 0u) {
+        const uint32_t matched = s[cur][HV_MAX_BLOCKS - 1u];
+        H.info[0] = min(matched, max_lanes); H.info[1] = matched;
+    }
+    if (t < HV_FIELDS) H.info[2u + t] = 0u;
+}
+
+__global__ __launch_bounds__(256) void k_harvest_emit(DevHarvest H, HarvestCounts C, uint32_t n, uint32_t chunk,
+                                                      uint32_t max_lanes) {
+    const uint32_t l = blockIdx.x * blockDim.x + threadIdx.x;
+    bool sel = false;
+    if (l < n) {
+        const uint32_t r = H.rank[l];
+        if (r != HV_NONE) {
+            const uint32_t g = H.boff[l / chunk] + r;        // <= l: the lanes below l that match
+            if (g < max_lanes) { H.list[g] = l; sel = true; }
+        }
+    }
+    if (!__ballot(sel)) return;                              // wave-uniform: nothing selected here
+#pragma unroll
+    for (uint32_t k = 0; k < HV_FIELDS; ++k) {
+        uint32_t v = sel && C.f[k] ? C.f[k][l] : 0u;
+#pragma unroll
+        for (uint32_t d = 32u; d; d >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, (int)d, 64));
+        if ((threadIdx.x & 63u) == 0u && v) atomicMax(&H.info[2u + k], v);
+    }
+}
+
+// ---- indexed gathers: device lane list[l0 + l], not first + l0 + l ---------------
+#define XP_MAX 24u
+struct PickTable {              // the scalar fields of one download
+    const void *src[XP_MAX];
+    uint32_t off[XP_MAX];       // byte offset of the field in the stage
+    uint32_t elem[XP_MAX];      // 4 or 8
+};
+
+// blockIdx.y = field; dst is 16-byte aligned and so is every off
+__global__ __launch_bounds__(256) void k_xfer_pick(PickTable P, const uint32_t *__restrict__ list, uint32_t n,
+                                                   uint8_t *__restrict__ dst) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, f = blockIdx.y;
+    if (i >= n) return;
+    const uint32_t lane = list[i];                           // < n_lanes (the invariant above)
+    if (P.elem[f] == 8u) ((uint64_t *)(dst + P.off[f]))[i] = ((const uint64_t *)P.src[f])[lane];
+    else ((uint32_t *)(dst + P.off[f]))[i] = ((const uint32_t *)P.src[f])[lane];
+}

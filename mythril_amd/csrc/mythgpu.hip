@@ -22,6 +22,7 @@
 #include "sym_step.cuh"
 #include "lane_fork.cuh"
 #include "lane_explore.cuh"
+#include "lane_harvest.cuh"
 #include "path_eval.cuh"
 #include "cc.h"
 
@@ -53,6 +54,9 @@ struct mg_ctx {
     DevExplore E{};                      // path planes and plan scratch (mg_explore_alloc), freed with the lanes
     ExploreCtr *d_ectr = nullptr;        // the round's counter block (with E)
     ExploreCtr *h_ectr = nullptr;        // its pinned host side (freed by mg_close)
+    DevHarvest H{};                      // mg_harvest_select's scratch and list (first use), freed with the lanes
+    bool hv_valid = false;               // a selection is resident (dropped by the three allocs)
+    mg_harvest_info hv{};                // what the last mg_harvest_select reported
     // mg_explore_check (path_eval.cuh): the node-value workspace and the call's arrays
     // (bindings | lane_binding | allowed | first_sat | sat_bits); outgrown ones retire
     uint4 *d_pws = nullptr;
@@ -248,6 +252,8 @@ static void free_lanes(mg_ctx *ctx) {
     ctx->S = DevSym{};
     ctx->T = DevTaint{};
     ctx->E = DevExplore{};
+    ctx->H = DevHarvest{};
+    ctx->hv_valid = false;
     ctx->d_ectr = nullptr;
     ctx->d_ctr = nullptr;
 }
@@ -598,6 +604,36 @@ __global__ __launch_bounds__(256) void k_xfer_gather(const uint32_t *__restrict_
         if (l < nl && c < cols) dst[(size_t)(l0 + l) * row + ((size_t)u0 << lgW) + c] = tile[l][c];
     }
 }
+// k_xfer_gather through a lane list (mg_harvest_download): stage row l0 + l is device
+// lane list[l0 + l].  The block's 64 entries are read once into LDS.  Every entry was
+// written by k_harvest_emit and is below n_lanes (lane_harvest.cuh states the
+// invariant), so the reads stay inside the plane as long as U is at most its capacity.
+template <bool BSWAP>
+__global__ __launch_bounds__(256) void k_xfer_gather_idx(const uint32_t *__restrict__ src, uint32_t n, uint32_t U,
+                                                        uint32_t lgW, uint32_t *__restrict__ dst, uint32_t N,
+                                                        const uint32_t *__restrict__ list) {
+    __shared__ uint32_t tile[XT_LANES][XT_COLS + 1];
+    __shared__ uint32_t lane_of[XT_LANES];
+    const uint32_t W = 1u << lgW, TU = XT_COLS >> lgW;
+    const uint32_t l0 = blockIdx.x * XT_LANES, u0 = blockIdx.y * TU;
+    const uint32_t nl = min(XT_LANES, n - l0), nu = min(TU, U - u0), cols = nu << lgW;
+    const size_t row = (size_t)U << lgW;
+    if (threadIdx.x < nl) lane_of[threadIdx.x] = list[l0 + threadIdx.x];
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < XT_LANES * XT_COLS; i += blockDim.x) {
+        const uint32_t uo = i / (XT_LANES * W), rem = i % (XT_LANES * W);
+        const uint32_t l = rem >> lgW, k = rem & (W - 1u);
+        if (uo < nu && l < nl) {
+            const uint32_t v = src[(((size_t)(u0 + uo) * N + lane_of[l]) << lgW) + k];
+            tile[l][(uo << lgW) + k] = BSWAP ? __builtin_bswap32(v) : v;
+        }
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < XT_LANES * XT_COLS; i += blockDim.x) {
+        const uint32_t l = i / XT_COLS, c = i % XT_COLS;
+        if (l < nl && c < cols) dst[(size_t)(l0 + l) * row + ((size_t)u0 << lgW) + c] = tile[l][c];
+    }
+}
 static uint32_t lg2(uint32_t w) { uint32_t r = 0; while ((1u << r) < w) ++r; return r; }
 static dim3 xfer_grid(uint32_t n, uint32_t U, uint32_t W) {
     return dim3((n + XT_LANES - 1) / XT_LANES, (U + (XT_COLS / W) - 1) / (XT_COLS / W));
@@ -643,7 +679,9 @@ struct XferPlan {
     bool bad = false;           // a field the transfer kernels cannot move
     size_t total = 0;
     uint32_t n = 0, first = 0;
+    const uint32_t *list = nullptr;     // download only: stage row i is device lane list[i], not first + i
     XferPlan(uint32_t n_, uint32_t first_) : n(n_), first(first_) {}
+    XferPlan(uint32_t n_, const uint32_t *list_) : n(n_), list(list_) {}
     void add(Item it) {
         if (!it.host) return;
         if (it.kind == SCALAR) it.len = (size_t)n * it.elem;
@@ -702,8 +740,31 @@ static int xfer_down(mg_ctx *ctx, const XferPlan &x) {
     if ((rc = ensure_stage(ctx, x.total)) || (rc = ensure_hxfer(ctx, x.total))) return rc;
     uint8_t *ds = (uint8_t *)ctx->d_stage;
     const uint32_t N = ctx->L.N;
+    if (x.list) {
+        // the scalars in one launch (a device-to-device copy cannot follow the list)
+        PickTable P{};
+        uint32_t np = 0;
+        for (const auto &it : x.items) {
+            if (it.kind != XferPlan::SCALAR || it.dev == (const void *)x.list) continue;
+            if (np == XP_MAX || (it.elem != 4 && it.elem != 8) || it.off > 0xffffffffu)
+                return set_err(ctx, MG_EINVAL, "lane transfer: scalar fields of an indexed download");
+            P.src[np] = it.dev; P.off[np] = (uint32_t)it.off; P.elem[np] = (uint32_t)it.elem;
+            ++np;
+        }
+        if (np) hipLaunchKernelGGL(k_xfer_pick, dim3(blocks_for(x.n), np), dim3(256), 0, ctx->stream, P, x.list, x.n, ds);
+    }
     for (const auto &it : x.items) {
-        if (it.kind == XferPlan::SCALAR) {
+        if (x.list) {
+            if (it.kind == XferPlan::UNITS)
+                hipLaunchKernelGGL(k_xfer_gather_idx<false>, xfer_grid(x.n, it.Uc, it.W), dim3(256), 0, ctx->stream,
+                                   (const uint32_t *)it.dev, x.n, it.Uc, lg2(it.W), (uint32_t *)(ds + it.off), N,
+                                   x.list);
+            else if (it.kind == XferPlan::BYTES)
+                hipLaunchKernelGGL(k_xfer_gather_idx<true>, xfer_grid(x.n, it.Uc, 1), dim3(256), 0, ctx->stream,
+                                   (const uint32_t *)it.dev, x.n, it.Uc, 0u, (uint32_t *)(ds + it.off), N, x.list);
+            else if (it.dev == (const void *)x.list)         // the list itself, as it is
+                HIPX(ctx, hipMemcpyAsync(ds + it.off, it.dev, it.len, hipMemcpyDeviceToDevice, ctx->stream));
+        } else if (it.kind == XferPlan::SCALAR) {
             HIPX(ctx, hipMemcpyAsync(ds + it.off, (const uint8_t *)it.dev + (size_t)x.first * it.elem, it.len,
                                      hipMemcpyDeviceToDevice, ctx->stream));
         } else if (it.kind == XferPlan::UNITS) {
@@ -887,6 +948,7 @@ extern "C" int mg_sym_alloc(mg_ctx *ctx, uint32_t node_cap, uint32_t const_cap) 
     if ((rc = get((void **)&S.sttag, (size_t)ctx->L.storage_cap * N * 8))) return rc;
     HIPX(ctx, hipStreamSynchronize(ctx->stream));
     ctx->S = S;
+    ctx->hv_valid = false;
     return MG_OK;
 }
 
@@ -1501,14 +1563,16 @@ extern "C" int mg_explore_alloc(mg_ctx *ctx, uint32_t path_cap) {
     E.boff = E.bt + 4u * EX_MAX_BLOCKS;
     HIPX(ctx, hipStreamSynchronize(ctx->stream));
     ctx->E = E;
+    ctx->hv_valid = false;
     return MG_OK;
 }
 
 // Per round: the stepping launch(es), three plan kernels, one D2H copy of the
 // counter block and one stream synchronisation, then at most three fork kernels.
-extern "C" int mg_explore(mg_ctx *ctx, const uint64_t hook_mask[4], uint32_t max_steps, uint32_t max_depth,
-                          uint32_t max_rounds, const uint32_t *free_lanes, uint32_t n_free,
-                          mg_explore_stats *stats) {
+// resume (mg_explore_resume): root, path_len and path stay; only the free marks restart.
+static int explore_run(mg_ctx *ctx, const uint64_t hook_mask[4], uint32_t max_steps, uint32_t max_depth,
+                       uint32_t max_rounds, const uint32_t *free_lanes, uint32_t n_free, mg_explore_stats *stats,
+                       bool resume) {
     if (!ctx) return MG_EINVAL;
     if (stats) *stats = mg_explore_stats{};
     if (!ctx->have_lanes) return set_err(ctx, MG_ESTATE, "mg_explore before mg_lanes_alloc");
@@ -1534,7 +1598,8 @@ extern "C" int mg_explore(mg_ctx *ctx, const uint64_t hook_mask[4], uint32_t max
         HIPX(ctx, hipMemcpyAsync(E.free, ctx->h_xfer, (size_t)n_free * 4u, hipMemcpyHostToDevice, ctx->stream));
     }
     HIPX(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-    hipLaunchKernelGGL(k_explore_init, dim3(blocks_for(n)), dim3(256), 0, ctx->stream, E, n);
+    if (resume) HIPX(ctx, hipMemsetAsync(E.isfree, 0, (size_t)n * 4u, ctx->stream));
+    else hipLaunchKernelGGL(k_explore_init, dim3(blocks_for(n)), dim3(256), 0, ctx->stream, E, n);
     if (n_free) hipLaunchKernelGGL(k_explore_mark, dim3(blocks_for(n_free)), dim3(256), 0, ctx->stream, E, n_free);
     HIPX(ctx, hipGetLastError());
     // block b of the plan owns lanes [b * chunk, (b + 1) * chunk): at most EX_MAX_BLOCKS totals
@@ -1591,6 +1656,18 @@ extern "C" int mg_explore(mg_ctx *ctx, const uint64_t hook_mask[4], uint32_t max
     return MG_OK;
 }
 
+extern "C" int mg_explore(mg_ctx *ctx, const uint64_t hook_mask[4], uint32_t max_steps, uint32_t max_depth,
+                          uint32_t max_rounds, const uint32_t *free_lanes, uint32_t n_free,
+                          mg_explore_stats *stats) {
+    return explore_run(ctx, hook_mask, max_steps, max_depth, max_rounds, free_lanes, n_free, stats, false);
+}
+
+extern "C" int mg_explore_resume(mg_ctx *ctx, const uint64_t hook_mask[4], uint32_t max_steps, uint32_t max_depth,
+                                 uint32_t max_rounds, const uint32_t *free_lanes, uint32_t n_free,
+                                 mg_explore_stats *stats) {
+    return explore_run(ctx, hook_mask, max_steps, max_depth, max_rounds, free_lanes, n_free, stats, true);
+}
+
 // path comes out lane-major, [n][path_cap]; entries at and above a lane's path_len are 0
 extern "C" int mg_explore_download(mg_ctx *ctx, uint32_t *path, uint32_t *path_len, uint32_t *root, uint32_t first,
                                    uint32_t n) {
@@ -1634,6 +1711,169 @@ extern "C" int mg_explore_upload(mg_ctx *ctx, const uint32_t *path, const uint32
     HIPX(ctx, hipMemcpy(E.path_len + first, path_len, (size_t)n * 4u, hipMemcpyHostToDevice));
     HIPX(ctx, hipMemcpy(E.root + first, root, (size_t)n * 4u, hipMemcpyHostToDevice));
     HIPX(ctx, hipMemcpy2D(E.path + first, N * 4u, rows.data(), (size_t)n * 4u, (size_t)n * 4u, cap, hipMemcpyHostToDevice));
+    return MG_OK;
+}
+
+// ---- mg_harvest_select / mg_harvest_download (lane_harvest.cuh) -----------------
+// Per call: a clear of the skip marks, the skip list's H2D copy and its mark kernel
+// (when there is one), three kernels, one D2H copy of the info block, one
+// synchronisation.  Nothing of the lane image is written.
+extern "C" int mg_harvest_select(mg_ctx *ctx, uint32_t status_mask, const uint32_t *skip, uint32_t n_skip,
+                                 uint32_t max_lanes, mg_harvest_info *info) {
+    if (!ctx) return MG_EINVAL;
+    if (info) *info = mg_harvest_info{};
+    if (!ctx->have_lanes) return set_err(ctx, MG_ESTATE, "mg_harvest_select before mg_lanes_alloc");
+    if (!ctx->uploaded) return set_err(ctx, MG_ESTATE, "mg_harvest_select before mg_lanes_upload");
+    if (!info) return set_err(ctx, MG_EINVAL, "mg_harvest_select: info is null");
+    const uint32_t n = ctx->L.n, N = ctx->L.N;
+    if (n_skip && !skip) return set_err(ctx, MG_EINVAL, "mg_harvest_select: skip is null with n_skip = %u", n_skip);
+    for (uint32_t j = 0; j < n_skip; ++j) {
+        if (skip[j] >= n)
+            return set_err(ctx, MG_EINVAL, "mg_harvest_select: skip[%u] = %u outside batch of %u", j, skip[j], n);
+        if (j && skip[j] <= skip[j - 1u])
+            return set_err(ctx, MG_EINVAL, "mg_harvest_select: skip[%u] = %u is not above skip[%u] = %u", j, skip[j],
+                           j - 1u, skip[j - 1u]);
+    }
+    HIPX(ctx, hipSetDevice(ctx->device));
+    DevHarvest &H = ctx->H;
+    int rc;
+    if (!H.list) {                       // first use for this batch; freed with the lanes
+        uint32_t *scratch = nullptr;     // skipm, skip, rank, list: [N] each; bt, boff; info
+        if ((rc = lane_alloc(ctx, scratch, (size_t)4u * N + 2u * HV_MAX_BLOCKS + 2u + HV_FIELDS))) return rc;
+        H.skipm = scratch; H.skip = scratch + N; H.rank = scratch + 2u * (size_t)N; H.list = scratch + 3u * (size_t)N;
+        H.bt = scratch + 4u * (size_t)N; H.boff = H.bt + HV_MAX_BLOCKS; H.info = H.boff + HV_MAX_BLOCKS;
+    }
+    ctx->hv_valid = false;
+    // MG_HARVEST_BLOCKS caps the scan blocks (a small batch can then cross both the tile carry and the offsets)
+    uint32_t max_blocks = HV_MAX_BLOCKS;
+    if (const char *e = getenv("MG_HARVEST_BLOCKS")) {
+        const long v = strtol(e, nullptr, 10);
+        if (v >= 1 && v <= (long)HV_MAX_BLOCKS) max_blocks = (uint32_t)v;
+    }
+    const uint32_t tiles = blocks_for(n);
+    const uint32_t chunk = ((tiles + max_blocks - 1u) / max_blocks) * 256u;
+    const uint32_t nb = (n + chunk - 1u) / chunk;            // <= max_blocks
+    const size_t info_off = ((size_t)n_skip * 4u + 15u) & ~(size_t)15u, info_bytes = (2u + HV_FIELDS) * 4u;
+    if ((rc = ensure_hxfer(ctx, info_off + info_bytes))) return rc;
+    HIPX(ctx, hipMemsetAsync(H.skipm, 0, (size_t)n * 4u, ctx->stream));
+    if (n_skip) {
+        std::memcpy(ctx->h_xfer, skip, (size_t)n_skip * 4u);
+        HIPX(ctx, hipMemcpyAsync(H.skip, ctx->h_xfer, (size_t)n_skip * 4u, hipMemcpyHostToDevice, ctx->stream));
+    }
+    HarvestCounts C{};
+    const DevLanes &L = ctx->L;
+    C.f[0] = L.sp; C.f[1] = L.msize; C.f[2] = L.storage_count;
+    C.f[3] = L.trace_cap ? L.trace_len : nullptr; C.f[4] = L.rec_cap ? L.rec_len : nullptr;
+    C.f[5] = ctx->S.node ? ctx->S.n_nodes : nullptr; C.f[6] = ctx->S.node ? ctx->S.n_consts : nullptr;
+    C.f[7] = ctx->E.path ? ctx->E.path_len : nullptr;
+    max_lanes = std::min(max_lanes, n);
+    HIPX(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    if (n_skip) hipLaunchKernelGGL(k_harvest_mark, dim3(blocks_for(n_skip)), dim3(256), 0, ctx->stream, H, n_skip);
+    hipLaunchKernelGGL(k_harvest_scan, dim3(nb), dim3(256), 0, ctx->stream, H, L.status, n, status_mask, chunk);
+    hipLaunchKernelGGL(k_harvest_totals, dim3(1), dim3(HV_MAX_BLOCKS), 0, ctx->stream, H, nb, max_lanes);
+    hipLaunchKernelGGL(k_harvest_emit, dim3(tiles), dim3(256), 0, ctx->stream, H, C, n, chunk, max_lanes);
+    HIPX(ctx, hipGetLastError());
+    HIPX(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+    HIPX(ctx, hipMemcpyAsync(ctx->h_xfer + info_off, H.info, info_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIPX(ctx, hipStreamSynchronize(ctx->stream));
+    mg_harvest_info out{};
+    std::memcpy(&out, ctx->h_xfer + info_off, info_bytes);   // n, matched and the maxima lead the struct
+    if (out.n > max_lanes || out.n > out.matched || out.matched > n)
+        return set_err(ctx, MG_EDEVICE, "mg_harvest_select: %u selected of %u matching over %u lanes (cap %u)", out.n,
+                       out.matched, n, max_lanes);
+    HIPX(ctx, hipEventElapsedTime(&out.kernel_ms, ctx->ev0, ctx->ev1));
+    ctx->hv = out;
+    ctx->hv_valid = true;
+    *info = out;
+    return MG_OK;
+}
+
+extern "C" int mg_harvest_download(mg_ctx *ctx, uint32_t *lanes, mg_lane_soa *h, mg_sym_soa *sym, uint32_t *path,
+                                   uint32_t *path_len, uint32_t *root) {
+    if (!ctx) return MG_EINVAL;
+    if (!ctx->have_lanes) return set_err(ctx, MG_ESTATE, "mg_harvest_download before mg_lanes_alloc");
+    if (!ctx->hv_valid)
+        return set_err(ctx, MG_ESTATE, "mg_harvest_download: no selection (mg_harvest_select first; an alloc drops it)");
+    const mg_harvest_info &I = ctx->hv;
+    const DevLanes &L = ctx->L;
+    const DevSym &S = ctx->S;
+    const DevExplore &E = ctx->E;
+    const uint32_t n = I.n;
+    if (!h || h->n != n)
+        return set_err(ctx, MG_EINVAL, "mg_harvest_download: host image of %u lanes for a selection of %u", h ? h->n : 0, n);
+    if (h->stack_cap > L.stack_cap || h->mem_cap > L.mem_cap || h->mem_cap % 4 || h->calldata_cap > L.calldata_cap ||
+        h->calldata_cap % 4 || h->storage_cap > L.storage_cap || h->trace_cap > L.trace_cap || h->rec_cap > L.rec_cap)
+        return set_err(ctx, MG_EINVAL, "mg_harvest_download: host image capacities exceed the batch configuration");
+    if (sym) {
+        if (!S.node) return set_err(ctx, MG_EINVAL, "mg_harvest_download: sym given without symbolic planes (mg_sym_alloc)");
+        if (sym->n != n || sym->stack_cap > L.stack_cap || sym->node_cap > S.node_cap || sym->const_cap > S.const_cap ||
+            sym->mem_cap > L.mem_cap || sym->storage_cap > L.storage_cap)
+            return set_err(ctx, MG_EINVAL, "mg_harvest_download: symbolic host image does not fit the selection or the allocation");
+    }
+    if (path && !E.path) return set_err(ctx, MG_EINVAL, "mg_harvest_download: path given without explore planes (mg_explore_alloc)");
+    if ((path != nullptr) != (path_len != nullptr) || (path != nullptr) != (root != nullptr))
+        return set_err(ctx, MG_EINVAL, "mg_harvest_download: path, path_len and root go together");
+    if (n == 0u) return MG_OK;
+    HIPX(ctx, hipSetDevice(ctx->device));
+    // every bound is the selection's largest count, clipped to the device capacity here and to
+    // the host's by the plan: the gathers stay inside the planes whatever the image holds now
+    const uint32_t b_sp = std::min(I.sp, L.stack_cap), b_ms = std::min(I.msize, L.mem_cap),
+                   b_st = std::min(I.storage_count, L.storage_cap), b_tr = std::min(I.trace_len, L.trace_cap),
+                   b_rec = std::min(I.rec_len, L.rec_cap);
+    XferPlan x(n, ctx->H.list);
+    // scalars first: k_xfer_pick takes their stage offsets as 32-bit words
+    x.scalar(lanes, ctx->H.list, 4);     // the list itself: copied, not picked (xfer_down)
+    x.scalar(h->code_id, L.code_id, 4);
+    x.scalar(h->pc, L.pc, 4);
+    x.scalar(h->sp, L.sp, 4);
+    x.scalar(h->msize, L.msize, 4);
+    x.scalar(h->depth, L.depth, 4);
+    x.scalar(h->status, L.status, 4);
+    x.scalar(h->aux, L.aux, 4);
+    x.scalar(h->steps, L.steps, 4);
+    x.scalar(h->flags, L.flags, 4);
+    x.scalar(h->calldata_len, L.calldata_len, 4);
+    x.scalar(h->storage_count, L.storage_count, 4);
+    x.scalar(h->ret_offset, L.ret_offset, 4);
+    x.scalar(h->ret_len, L.ret_len, 4);
+    x.scalar(h->gas_min, L.gas_min, 8);
+    x.scalar(h->gas_max, L.gas_max, 8);
+    x.scalar(h->gas_limit, L.gas_limit, 8);
+    if (h->trace_cap) x.scalar(h->trace_len, L.trace_len, 4);
+    if (h->rec_cap) x.scalar(h->rec_len, L.rec_len, 4);
+    if (h->fent) x.scalar(h->fent, L.fent, 4);
+    if (sym) {
+        x.scalar(sym->n_nodes, S.n_nodes, 4);
+        x.scalar(sym->n_consts, S.n_consts, 4);
+    }
+    if (path) {
+        x.scalar(path_len, E.path_len, 4);
+        x.scalar(root, E.root, 4);
+    }
+    x.units(h->stack, h->stack_cap, 8, L.stack, b_sp);
+    x.units(h->env, MG_ENV_WORDS, 8, L.env);
+    x.units(h->storage, h->storage_cap, 16, L.storage, b_st);
+    x.bytes(h->memory, h->mem_cap, L.mem, (b_ms + 3u) / 4u);
+    x.bytes(h->calldata, h->calldata_cap, L.calldata);
+    if (h->trace_cap) x.units(h->trace, h->trace_cap, 1, L.trace, b_tr);
+    if (h->rec_cap) x.units(h->rec, h->rec_cap, 1, L.rec, b_rec);
+    if (sym) {
+        x.units(sym->stag, sym->stack_cap, 1, S.stag, b_sp);
+        x.units(sym->node, sym->node_cap, 4, S.node, std::min(I.n_nodes, S.node_cap));
+        x.units(sym->cval, sym->const_cap, 8, S.cval, std::min(I.n_consts, S.const_cap));
+        x.units(sym->mtag, sym->mem_cap, 1, S.mtag, b_ms);
+        x.units(sym->sttag, sym->storage_cap, 2, S.sttag, b_st);
+    }
+    const uint32_t b_path = path ? std::min(I.path_len, E.path_cap) : 0u;
+    if (path) x.units(path, E.path_cap, 1, E.path, b_path);
+    int rc;
+    if ((rc = xfer_down(ctx, x))) return rc;
+    if (path) {
+        // the plane above a lane's path_len holds what an earlier owner of the lane left
+        const size_t cap = E.path_cap;
+        for (uint32_t i = 0; i < n; ++i)
+            for (size_t e = std::min(path_len[i], b_path); e < cap; ++e) path[(size_t)i * cap + e] = 0u;
+    }
     return MG_OK;
 }
 

@@ -39,6 +39,23 @@ class ExploreStats:
     kernel_ms: float
 
 
+@dataclass
+class HarvestInfo:
+    """mg_harvest_info: n lanes selected of `matched`, and the largest counts among
+    the selected lanes (the bounds of harvest_download)."""
+    n: int
+    matched: int
+    sp: int
+    msize: int
+    storage_count: int
+    trace_len: int
+    rec_len: int
+    n_nodes: int
+    n_consts: int
+    path_len: int
+    kernel_ms: float
+
+
 def _mask_array(hook_mask: Optional[Sequence[int]]):
     m = list(hook_mask) if hook_mask is not None else [0, 0, 0, 0]
     return (ctypes.c_uint64 * 4)(*[int(x) & ((1 << 64) - 1) for x in m])
@@ -217,15 +234,16 @@ class GpuDevice:
         self.path_cap = int(path_cap)
 
     def explore(self, free, hook_mask=None, max_steps: int = 1 << 30, max_depth: int = 0,
-                max_rounds: int = 64) -> ExploreStats:
+                max_rounds: int = 64, resume: bool = False) -> ExploreStats:
         """mg_explore: up to `max_rounds` rounds of step + fork on the device.  `free`:
         the lanes that may be overwritten with jump successors, strictly ascending;
-        they are handed out from the front, stats.free_used of them."""
+        they are handed out from the front, stats.free_used of them.  resume=True
+        (mg_explore_resume): root, path_len and path continue from the last call."""
         arr = np.ascontiguousarray(np.asarray(free, dtype=np.uint32).reshape(-1))
         st = native.MgExploreStats()
-        self._check(self.lib.mg_explore(self.ctx, _mask_array(hook_mask), max_steps, max_depth, int(max_rounds),
-                                        arr.ctypes.data if arr.size else None, arr.size, ctypes.byref(st)),
-                    "mg_explore")
+        fn, name = (self.lib.mg_explore_resume, "mg_explore_resume") if resume else (self.lib.mg_explore, "mg_explore")
+        self._check(fn(self.ctx, _mask_array(hook_mask), max_steps, max_depth, int(max_rounds),
+                       arr.ctypes.data if arr.size else None, arr.size, ctypes.byref(st)), name)
         return ExploreStats(st.rounds, st.forks, st.made_jump, st.starved, st.path_full, st.free_used, st.running,
                             st.lane_steps, st.kernel_ms)
 
@@ -250,6 +268,61 @@ class GpuDevice:
             raise ValueError("explore_upload_paths: path is [n, path_cap], path_len and root are [n]")
         self._check(self.lib.mg_explore_upload(self.ctx, path.ctypes.data, path_len.ctypes.data, root.ctypes.data,
                                                first, n), "mg_explore_upload")
+
+    def harvest_select(self, status_mask: int, skip=(), max_lanes: Optional[int] = None) -> HarvestInfo:
+        """mg_harvest_select: choose on the device the lanes whose status bit is set in
+        `status_mask` and that are not in `skip` (the caller's free list, strictly
+        ascending), the lowest `max_lanes` of them (None: all).  The list stays on
+        the device for harvest_download."""
+        arr = np.ascontiguousarray(np.asarray(skip, dtype=np.uint32).reshape(-1))
+        info = native.MgHarvestInfo()
+        cap = 0xFFFFFFFF if max_lanes is None else int(max_lanes)
+        self._check(self.lib.mg_harvest_select(self.ctx, int(status_mask) & 0xFFFFFFFF,
+                                               arr.ctypes.data if arr.size else None, arr.size, cap,
+                                               ctypes.byref(info)), "mg_harvest_select")
+        return HarvestInfo(info.n, info.matched, info.sp, info.msize, info.storage_count, info.trace_len,
+                           info.rec_len, info.n_nodes, info.n_consts, info.path_len, info.kernel_ms)
+
+    def harvest_shape(self, info: HarvestInfo) -> LaneShape:
+        """The slim shape harvest_download builds by default: info's maxima as the
+        capacities (mem_cap rounded up to 32, stack_cap at least 1), the device's
+        calldata capacity, symbolic planes when the batch has them."""
+        d = self.shape
+        return LaneShape(n=info.n, stack_cap=max(info.sp, 1), mem_cap=(info.msize + 31) // 32 * 32,
+                         calldata_cap=d.calldata_cap, storage_cap=info.storage_count,
+                         trace_cap=info.trace_len if d.trace_cap else 0, rec_cap=info.rec_len if d.rec_cap else 0,
+                         node_cap=max(info.n_nodes, 1) if d.node_cap else 0,
+                         const_cap=max(info.n_consts, 1) if d.node_cap else 0)
+
+    def harvest_download(self, info: HarvestInfo, shape: Optional[LaneShape] = None, batch: Optional[LaneBatch] = None):
+        """mg_harvest_download of the last harvest_select: (lanes uint32[n], LaneBatch of
+        n lanes, path uint32[n, path_cap], path_len, root); row i is device lane
+        lanes[i].  The image is `batch` when given (its cells above the bounds are
+        kept), else a new one of `shape` (default: harvest_shape(info)).  path,
+        path_len and root are None without explore planes."""
+        n = info.n
+        if batch is None:
+            batch = LaneBatch(shape if shape is not None else self.harvest_shape(info))
+        if batch.n != n:
+            raise ValueError("harvest_download: the host image has one lane per selected lane")
+        lanes = np.zeros(n, dtype=np.uint32)
+        path = path_len = root = None
+        if self.path_cap:
+            path = np.zeros((n, self.path_cap), dtype=np.uint32)
+            path_len = np.zeros(n, dtype=np.uint32)
+            root = np.zeros(n, dtype=np.uint32)
+        soa = batch.soa()
+        sym = batch.sym_soa_range(0, n) if batch.symbolic else None
+        self._check(self.lib.mg_harvest_download(
+            self.ctx, lanes.ctypes.data, ctypes.addressof(soa), ctypes.addressof(sym) if sym is not None else None,
+            path.ctypes.data if path is not None else None, path_len.ctypes.data if path is not None else None,
+            root.ctypes.data if path is not None else None), "mg_harvest_download")
+        return lanes, batch, path, path_len, root
+
+    def harvest(self, status_mask: int, skip=(), max_lanes: Optional[int] = None, shape: Optional[LaneShape] = None):
+        """harvest_select + harvest_download: (info, lanes, LaneBatch, path, path_len, root)."""
+        info = self.harvest_select(status_mask, skip, max_lanes)
+        return (info,) + self.harvest_download(info, shape)
 
     def explore_check(self, pool, bindings, lane_binding, allowed=None, first: int = 0, n: Optional[int] = None,
                       bits: bool = False, functions=None):

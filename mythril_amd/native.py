@@ -121,6 +121,14 @@ class MgExploreStats(ctypes.Structure):
                 ("kernel_ms", ctypes.c_float), ("_padf", ctypes.c_float)]
 
 
+class MgHarvestInfo(ctypes.Structure):
+    """mg_harvest_info: the selection's size and the largest counts among its lanes."""
+    _fields_ = [("n", ctypes.c_uint32), ("matched", ctypes.c_uint32), ("sp", ctypes.c_uint32),
+                ("msize", ctypes.c_uint32), ("storage_count", ctypes.c_uint32), ("trace_len", ctypes.c_uint32),
+                ("rec_len", ctypes.c_uint32), ("n_nodes", ctypes.c_uint32), ("n_consts", ctypes.c_uint32),
+                ("path_len", ctypes.c_uint32), ("kernel_ms", ctypes.c_float), ("_pad", ctypes.c_uint32)]
+
+
 class MgPathBinding(ctypes.Structure):
     """mg_path_binding: where one lineage's symbols live in the model batch
     (abi.MG_PATH_UNBOUND: not bound)."""
@@ -173,6 +181,9 @@ SIGNATURES = {
     "mg_lanes_fork": (_I, [_P, ctypes.POINTER(MgForkBatch), _P, _P, ctypes.POINTER(ctypes.c_float)]),
     "mg_explore_alloc": (_I, [_P, _U32]),
     "mg_explore": (_I, [_P, _P, _U32, _U32, _U32, _P, _U32, ctypes.POINTER(MgExploreStats)]),
+    "mg_explore_resume": (_I, [_P, _P, _U32, _U32, _U32, _P, _U32, ctypes.POINTER(MgExploreStats)]),
+    "mg_harvest_select": (_I, [_P, _U32, _P, _U32, _U32, ctypes.POINTER(MgHarvestInfo)]),
+    "mg_harvest_download": (_I, [_P, _P, _P, _P, _P, _P, _P]),
     "mg_explore_download": (_I, [_P, _P, _P, _P, _U32, _U32]),
     "mg_explore_upload": (_I, [_P, _P, _P, _P, _U32, _U32]),
     "mg_explore_check": (_I, [_P, ctypes.POINTER(MgModelBatch), _P, _U32, _P, _P, _U32, _U32, _P, _P,
