@@ -46,6 +46,17 @@ enum {
  *   MS_EXTRACT: p0 = hi, p1 = lo; MS_ZERO_EXTEND / MS_SIGN_EXTEND: p0 = bits added
  * roots: 1-bit nodes asserted true.  minimize: bit-vector nodes minimised in
  * order (lexicographic), after satisfiability.
+ *
+ * Every node must be well-sorted, or the call returns MS_EINVAL before anything
+ * is blasted: the operand count of its opcode; operands of the node's width for
+ * the arithmetic, bitwise and shift operators; equal operand widths and width 1
+ * for comparisons and the overflow predicates; 1-bit operands for the Boolean
+ * connectives; MS_ITE: a 1-bit condition and arms of the node's width;
+ * MS_CONCAT: operand widths summing to the width; extensions: p0 + operand
+ * width == width; MS_EXTRACT: lo <= hi < operand width, hi - lo + 1 == width;
+ * MS_SELECT / MS_STORE: an array-sorted first operand of the same range, an
+ * index of the width the array was first indexed with, a stored value of the
+ * range width; MS_UF: the widths of the function's first application.
  */
 typedef struct {
     uint32_t n_nodes;

@@ -794,20 +794,34 @@ public:
     // table, their first_arg / constant limbs local to the query's arrays).
     bool append(const ms_query &q) {
         const uint32_t base = n_nodes;
+        // a rejected query leaves the table as it found it
+        const size_t nodes0 = nodes_.size(), args0 = args_.size(), limbs0 = limbs_.size();
+        const auto dom0 = array_dom;
+        const auto sig0 = func_sig;
+        auto reject = [&]() {
+            nodes_.resize(nodes0);
+            args_.resize(args0);
+            limbs_.resize(limbs0);
+            array_dom = dom0;
+            func_sig = sig0;
+            return false;
+        };
         for (uint32_t k = 0; k < q.n_nodes; ++k) {
             const uint32_t *n = q.nodes + 6 * (size_t)k;
-            if (n[0] >= MS_N_OPS) return false;
+            if (n[0] >= MS_N_OPS) return reject();
             uint32_t row[6] = {n[0], n[1], n[2], (uint32_t)args_.size(), n[4], n[5]};
             for (uint32_t i = 0; i < n[2]; ++i) {
                 uint32_t a = q.args[n[3] + i];
-                if (a >= base + k) return false;                     // post order
+                if (a >= base + k) return reject();                  // post order
                 args_.push_back(a);
             }
+            if (!well_sorted(row)) return reject();
             if (n[0] == MS_CONST) {
+                if (!q.limbs) return reject();
                 row[4] = (uint32_t)limbs_.size();
                 limbs_.insert(limbs_.end(), q.limbs + n[4], q.limbs + n[4] + (n[1] + 31) / 32);
             }
-            if (n[0] == MS_VAR && n[4] >= q.n_vars) return false;
+            if (n[0] == MS_VAR && n[4] >= q.n_vars) return reject();
             nodes_.insert(nodes_.end(), row, row + 6);
         }
         n_nodes = base + q.n_nodes;
@@ -821,6 +835,101 @@ public:
         aff.resize(n_nodes);
         aff_done.resize(n_nodes, 0);
         return true;
+    }
+
+    // The sort of every node is checked as it is appended: blast() indexes each
+    // operand up to the width its operator implies (a[i], b[i] for i < w), so an
+    // operand of another width reads outside its bits.  Words have width >= 1;
+    // MS_ARRAY / MS_K / MS_STORE are array-sorted (width 0, the range in p1) and
+    // are operands of MS_SELECT and MS_STORE only.  An array's domain is the
+    // width of the first index it is read or stored at, a function's signature
+    // that of its first application; later uses must agree.
+    std::unordered_map<uint32_t, uint32_t> array_dom;                 // array id -> domain width
+    std::unordered_map<uint32_t, std::vector<uint32_t>> func_sig;     // function id -> argument widths, range
+
+    static bool array_sorted(uint32_t op) { return op == MS_ARRAY || op == MS_K || op == MS_STORE; }
+
+    // The domain an array-sorted node is known to have (0: not known yet).
+    uint32_t domain_of(uint32_t k) const {
+        const uint32_t *n = node(k);
+        if (n[0] == MS_STORE) return node(args_[n[3] + 1])[1];
+        if (n[0] == MS_ARRAY) {
+            auto it = array_dom.find(n[4]);
+            return it == array_dom.end() ? 0u : it->second;
+        }
+        return 0u;                                                    // MS_K: any domain
+    }
+    // An index of width `iw` into the array-sorted node k: its domain, if known,
+    // must be iw; the symbolic array at the chain's root learns it otherwise.
+    bool index_fits(uint32_t k, uint32_t iw) {
+        uint32_t d = domain_of(k);
+        if (d) return d == iw;
+        while (node(k)[0] == MS_STORE) k = args_[node(k)[3]];
+        if (node(k)[0] == MS_ARRAY) array_dom[node(k)[4]] = iw;
+        return true;
+    }
+
+    // row: the node about to be appended (its arguments already in args_).
+    bool well_sorted(const uint32_t *row) {
+        const uint32_t op = row[0], w = row[1], na = row[2];
+        auto a_op = [&](uint32_t i) { return node(args_[row[3] + i])[0]; };
+        auto a_w = [&](uint32_t i) { return node(args_[row[3] + i])[1]; };     // 0: array-sorted
+        auto words = [&](uint32_t count, uint32_t width) {                       // `count` operands, each `width` bits
+            if (na != count || width == 0) return false;
+            for (uint32_t i = 0; i < na; ++i)
+                if (a_w(i) != width) return false;
+            return true;
+        };
+        switch (op) {
+        case MS_CONST: case MS_VAR:
+            return na == 0 && w >= 1;
+        case MS_ARRAY:
+            return na == 0 && w == 0 && row[5] >= 1;
+        case MS_BVADD: case MS_BVSUB: case MS_BVMUL: case MS_BVUDIV: case MS_BVUREM: case MS_BVSDIV:
+        case MS_BVSREM: case MS_BVSMOD: case MS_BVAND: case MS_BVOR: case MS_BVXOR: case MS_BVSHL:
+        case MS_BVLSHR: case MS_BVASHR:
+            return words(2, w);
+        case MS_BVNOT: case MS_BVNEG:
+            return words(1, w);
+        case MS_EQ: case MS_DISTINCT: case MS_BVULT: case MS_BVULE: case MS_BVUGT: case MS_BVUGE:
+        case MS_BVSLT: case MS_BVSLE: case MS_BVSGT: case MS_BVSGE: case MS_BVADD_NOOVFL_U:
+        case MS_BVUMUL_NOOVFL: case MS_BVSUB_NOUDFL_U:
+            return w == 1 && na == 2 && words(2, a_w(0));
+        case MS_AND: case MS_OR:
+            return w == 1 && na >= 1 && words(na, 1);
+        case MS_NOT:
+            return w == 1 && words(1, 1);
+        case MS_XOR: case MS_IMPLIES:
+            return w == 1 && words(2, 1);
+        case MS_ITE:
+            return na == 3 && w >= 1 && a_w(0) == 1 && a_w(1) == w && a_w(2) == w;
+        case MS_CONCAT:
+            return na == 2 && a_w(0) >= 1 && a_w(1) >= 1 && (uint64_t)a_w(0) + a_w(1) == w;
+        case MS_EXTRACT:
+            return na == 1 && row[5] <= row[4] && row[4] < a_w(0) && row[4] - row[5] + 1 == w;
+        case MS_ZERO_EXTEND: case MS_SIGN_EXTEND:
+            return na == 1 && a_w(0) >= 1 && (uint64_t)row[4] + a_w(0) == w;
+        case MS_SELECT:
+            return na == 2 && w >= 1 && array_sorted(a_op(0)) && node(args_[row[3]])[5] == w && a_w(1) >= 1 &&
+                   index_fits(args_[row[3]], a_w(1));
+        case MS_K:
+            return w == 0 && row[5] >= 1 && words(1, row[5]);
+        case MS_STORE:
+            return na == 3 && w == 0 && row[5] >= 1 && array_sorted(a_op(0)) && node(args_[row[3]])[5] == row[5] &&
+                   a_w(1) >= 1 && a_w(2) == row[5] && index_fits(args_[row[3]], a_w(1));
+        case MS_UF: {
+            if (w == 0) return false;
+            std::vector<uint32_t> sig;
+            for (uint32_t i = 0; i < na; ++i) {
+                if (a_w(i) == 0) return false;
+                sig.push_back(a_w(i));
+            }
+            sig.push_back(w);
+            auto it = func_sig.emplace(row[4], sig).first;
+            return it->second == sig;
+        }
+        default: return false;
+        }
     }
 
     // Word-level index reasoning: calldata and memory reads at `p + k` for one

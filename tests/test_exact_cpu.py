@@ -18,12 +18,12 @@ from pathlib import Path
 
 import pytest
 
+import exact_rand
 from mythril_amd.smt import exact
 from mythril_amd.smt import expr as E
 from mythril_amd.smt.expr import (UGT, ULT, And, Array, Concat, Function, Not, Or, BVAddNoOverflow,
                                   BVMulNoOverflow, BVSubNoUnderflow, symbol_factory as sf)
 from mythril_amd.smt.program import ArrayInterp, FuncInterp
-from mythril_amd.smt.solver import ModelRef
 
 HERE = Path(__file__).resolve().parent
 
@@ -34,85 +34,10 @@ def solver():
     return exact.ExactSolver(max_ms=20000)
 
 
-def holds(assign, conj):
-    m = ModelRef(assign)
-    return all(m.eval(c, model_completion=True).param == 1 for c in conj)
-
-
 W = 4
-BIN = ["bvadd", "bvsub", "bvmul", "bvudiv", "bvurem", "bvsdiv", "bvsrem", "bvsmod", "bvand", "bvor", "bvxor",
-       "bvshl", "bvlshr", "bvashr"]
-CMP = ["eq", "distinct", "bvult", "bvule", "bvugt", "bvuge", "bvslt", "bvsle", "bvsgt", "bvsge",
-       "bvadd_noovfl_u", "bvumul_noovfl", "bvsub_noudfl_u"]
-
-
-def rand_bv(rng, leaves, depth):
-    if depth == 0 or rng.random() < 0.25:
-        if rng.random() < 0.3:
-            return E.const(rng.randrange(1 << W), W)
-        return rng.choice(leaves)
-    k = rng.random()
-    if k < 0.55:
-        return E._fold(rng.choice(BIN), W, (rand_bv(rng, leaves, depth - 1), rand_bv(rng, leaves, depth - 1)))
-    if k < 0.62:
-        return E._fold(rng.choice(["bvnot", "bvneg"]), W, (rand_bv(rng, leaves, depth - 1),))
-    if k < 0.75:
-        return E._fold("ite", W, (rand_bool(rng, leaves, depth - 1), rand_bv(rng, leaves, depth - 1),
-                                  rand_bv(rng, leaves, depth - 1)))
-    if k < 0.85:
-        # extract + extend / concat back to W bits
-        a = rand_bv(rng, leaves, depth - 1)
-        lo = rng.randrange(W)
-        hi = rng.randrange(lo, W)
-        x = E._fold("extract", hi - lo + 1, (a,), (hi, lo))
-        if hi - lo + 1 == W:
-            return x
-        if rng.random() < 0.5:
-            return E._fold(rng.choice(["zero_extend", "sign_extend"]), W, (x,), W - (hi - lo + 1))
-        rest = W - (hi - lo + 1)
-        b = E._fold("extract", rest, (rand_bv(rng, leaves, depth - 1),), (rest - 1, 0))
-        return E._fold("concat", W, (x, b))
-    if k < 0.93:
-        return E._select(ARR_RAW[0], rand_bv(rng, leaves, depth - 1))
-    return FUNC(sf.BitVecVal(0, W) + E.BitVec(rand_bv(rng, leaves, depth - 1))).raw
-
-
-def rand_bool(rng, leaves, depth):
-    k = rng.random()
-    if depth == 0 or k < 0.6:
-        return E._fold(rng.choice(CMP), 1, (rand_bv(rng, leaves, depth - 1 if depth else 0),
-                                           rand_bv(rng, leaves, depth - 1 if depth else 0)))
-    if k < 0.75:
-        return E._fold("not", 1, (rand_bool(rng, leaves, depth - 1),))
-    if k < 0.9:
-        op = rng.choice(["and", "or"])
-        return E.Node(op, 1, (rand_bool(rng, leaves, depth - 1), rand_bool(rng, leaves, depth - 1)))
-    return E._fold(rng.choice(["xor", "implies"]), 1, (rand_bool(rng, leaves, depth - 1),
-                                                      rand_bool(rng, leaves, depth - 1)))
-
-
-ARR = Array("mem4", W, W)
-ARR_RAW = [ARR.raw]
-FUNC = Function("f4", [W], W)
-
-
-def enumerate_models(conj, names):
-    uses_arr = any("mem4" in repr(c) for c in conj)
-    uses_f = any("f4" in repr(c) for c in conj)
-    vals = range(1 << W)
-    tables = [None]
-    if uses_arr or uses_f:
-        # the reads' indices range over all 16 points: enumerate a table as 16
-        # values drawn from a small alphabet -- exhaustive over {0, 5} per point
-        tables = list(itertools.product((0, 5), repeat=1 << W))
-    for xs in itertools.product(vals, repeat=len(names)):
-        base = dict(zip(names, xs))
-        for tab in tables:
-            a = dict(base)
-            if tab is not None:
-                a["mem4"] = ArrayInterp(0, dict(enumerate(tab)))
-                a["f4"] = FuncInterp(0, {(i,): v for i, v in enumerate(tab)})
-            yield a
+GEN = exact_rand.Gen(W)           # the generator and brute force, shared with test_exact_words_cpu.py
+holds = exact_rand.holds
+rand_bv, rand_bool, enumerate_models = GEN.rand_bv, GEN.rand_bool, GEN.enumerate_models
 
 
 @pytest.mark.parametrize("seed", range(8))
