@@ -399,7 +399,9 @@ int         mg_sym_download(mg_ctx *ctx, mg_sym_soa *host, uint32_t first, uint3
  *
  * Batch-safe hooks (mythril_amd/laser/taint.py) become per-opcode actions the
  * device applies instead of yielding to the host, and log an MG_REC_ANNOT record
- * per new atom.  Action word per opcode byte (mg_taint_program): */
+ * per new atom.  No action applies to an instruction that has fewer stack
+ * words than its opcode requires: it raises before any hook runs
+ * (svm.py:391-405).  Action word per opcode byte (mg_taint_program): */
 #define MG_TAINT_PRE_SHIFT   0   /* bits 0..3: operand k + 1 of a pre-hook that annotates stack[-1-k] */
 #define MG_TAINT_POST       16u  /* a post-hook annotates the pushed word                     */
 #define MG_TAINT_EXPCOND    32u  /* skip the pre-annotation when stack[-2] == 0 or stack[-1] < 2

@@ -465,6 +465,9 @@ __global__ __launch_bounds__(256) void k_sym_step(DevLanes L, DevSym S, DevTaint
             if (f == 1u) { status = MG_HOOK; aux = op; break; }
             if (f == 2u) tact = 0u;
         }
+        // an instruction short of its required stack words raises before any of its
+        // hooks runs (svm.py:391-402 precede the pre-hooks of :405)
+        if (sp < req) tact = 0u;
         if (tact) {
             const uint32_t pre_k = MG_TAINT_FIELD(tact, MG_TAINT_PRE_SHIFT);
             const uint32_t yk = MG_TAINT_FIELD(tact, MG_TAINT_YIELD_SHIFT);
@@ -482,7 +485,7 @@ __global__ __launch_bounds__(256) void k_sym_step(DevLanes L, DevSym S, DevTaint
                 for (uint32_t j = 0; j < dk && j < sp; ++j) ysym |= sym_tag(S, N, lane, sp - 1u - j) != 0u;
             }
             if (ysym || ((tact & MG_TAINT_IFLANE) && (ttf & 2u))) { status = MG_HOOK; aux = op; break; }
-            bool do_pre = pre_k != 0u && sp >= pre_k && sp >= req;
+            bool do_pre = pre_k != 0u && sp >= pre_k;
             const bool do_post = (tact & MG_TAINT_POST) != 0u;
             if (do_pre || do_post) {
                 // the device replays annotating hooks on concrete words only; the host

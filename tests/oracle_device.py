@@ -35,6 +35,7 @@ class OracleDevice:
         self.shape = None
         self._actions = np.zeros(256, dtype=np.uint32)
         self._force = {}
+        self.taint_watch = None      # {lane: counters} of the restatement (tests/taintref.py), when a dict
 
     # -- codes
     def load_code(self, code: bytes) -> int:
@@ -128,8 +129,9 @@ class OracleDevice:
         mask = hook_mask or (0, 0, 0, 0)
         for i in tl:
             ops, _ = self.o.code_table(int(img.code_id[i]))
+            watch = None if self.taint_watch is None else self.taint_watch.setdefault(int(i), {})
             steps += run_lane(self.o, ops, img, int(i), self._actions, mask, max_steps, max_depth, horizon, bound,
-                              self._force.get(int(img.code_id[i])))
+                              self._force.get(int(img.code_id[i])), watch)
         for cid in self._cov:
             self.o.set_coverage(cid, None)
         s = self._img.status

@@ -37,11 +37,12 @@ from typing import Dict, List
 
 import numpy as np
 
+from mythril_amd.laser.opcodes import ADDRESS_OPCODE_MAPPING, get_required_stack_elements
 from mythril_amd.lanes import (MG_ESC_OPCODE, MG_ESC_RECORD, MG_ESC_TAINT, MG_ESCAPE, MG_HOOK,
                                MG_LANE_HOOK_ACK, MG_LANE_STEP1, MG_REC_ANNOT, MG_REC_ANNOT_WORDS, MG_REC_HOOK,
                                MG_TAINT_IFLANE,
                                MG_REC_HEADER, MG_RUNNING, MG_TAINT_CDSIZE, MG_TAINT_EXPCOND,
-                               MG_TAINT_OBJ0, MG_TAINT_POST, MG_TAINT_YCLASS, limbs_to_word,
+                               MG_TAINT_OBJ0, MG_TAINT_POST, MG_TAINT_YCLASS, MG_VMEXC, limbs_to_word,
                                word_to_limbs)
 
 ENV_OPS = {0x30: 1, 0x33: 2, 0x32: 3, 0x34: 4, 0x3A: 5}
@@ -81,7 +82,7 @@ class RefLane:
         self.fixed: Dict[int, Obj] = {}
         self.env: Dict[int, Obj] = {}
         for h in range(1, MG_TAINT_CDSIZE + 1):
-            self.env[h] = Obj(_bits(b.omask[i, h]))
+            self.env[h] = Obj(_bits(b.omask[i, h]), tracked=True)
         self.stack: List[Obj] = []
         for s in range(int(b.sp[i])):
             h = int(b.sobj[i, s])
@@ -95,6 +96,10 @@ class RefLane:
                 self.stack.append(self.fixed[h])
         self.n_fixed = int(b.n_fixed[i])
         self.n_obj = int(b.n_obj[i])
+        # the host's handles no stack slot holds: compaction leaves them alone
+        self.host_dead = {h: int(b.omask[i, h]) for h in range(MG_TAINT_OBJ0, self.n_fixed)
+                          if h not in self.fixed}
+        self.allocs = 0             # handles the device has taken since (t_new), dead ones too
         self.natoms = int(b.n_atoms[i])
         self.sink = _bits(b.sink[i])
         self.tflags = int(b.tflags[i])
@@ -107,6 +112,8 @@ class RefLane:
         b.omask[i] = 0
         for h, o in self.env.items():
             b.omask[i, h] = _mask(o.ann)
+        for h, m in self.host_dead.items():
+            b.omask[i, h] = m
         handle = {id(o): h for h, o in self.env.items()}
         for h, o in self.fixed.items():
             handle[id(o)] = h
@@ -188,7 +195,7 @@ def _restore(b, i, snap):
 
 
 def step_lane(oracle, ops: np.ndarray, b, i: int, lane: RefLane, actions, hook_mask, max_depth: int,
-              acked: bool, loop_bound: int = 0, force=None) -> bool:
+              acked: bool, loop_bound: int = 0, force=None, watch=None) -> bool:
     """One instruction of taint lane i (its objects in `lane`), in k_sym_step's
     order: depth / end / trace and loop bound / hook / opcode escape, then the
     batch-safe hooks' checks, then the mutator.  Returns whether it executed;
@@ -199,13 +206,16 @@ def step_lane(oracle, ops: np.ndarray, b, i: int, lane: RefLane, actions, hook_m
     snap = _snap(b, i)
     if acked or pc >= ops.size:
         # the host already ran this instruction's hooks: no device actions
+        if watch is not None:
+            watch["nobj_peak"] = max(watch.get("nobj_peak", 0), lane.n_obj + lane.allocs)
         if acked and pc < ops.size and _objects_full(lane, b.shape.obj_cap):
             b.status[i], b.aux[i] = MG_ESCAPE, int(ops[pc]) | (MG_ESC_TAINT << 8)
             return False
         oracle.run(b, i, 1, hook_mask=hook_mask, max_steps=1, max_depth=max_depth, loop_bound=loop_bound)
         if int(b.steps[i]) != steps0 + 1:
             return False
-        _objects(b, i, lane, int(ops[pc]), pc, sp, 0, None, None, snap)
+        if int(b.status[i]) != MG_VMEXC:        # a VmException counts as a step, but nothing ran
+            _objects(b, i, lane, int(ops[pc]), pc, sp, 0, None, None, snap)
         return True
     op = int(ops[pc])
     # probe: stop the lane right before the mutator (traced like any popped instruction)
@@ -225,11 +235,19 @@ def step_lane(oracle, ops: np.ndarray, b, i: int, lane: RefLane, actions, hook_m
     _restore(b, i, at_op)
     b.status[i], b.aux[i] = MG_RUNNING, 0
     tact = int(actions[op])
+    if watch is not None and tact:
+        watch["reached"] = watch.get("reached", 0) + 1
     if tact and force is not None and force[pc] == 1:
         b.status[i], b.aux[i] = MG_HOOK, op          # a cached issue address: the host's hooks
         return False
     if tact and force is not None and force[pc] == 2:
         tact = 0                                     # every module returns early there
+    # svm.py:391-402: an instruction short of its required stack elements raises the
+    # stack underflow before any of its hooks runs (the pre-hooks are at :405)
+    if sp < get_required_stack_elements(ADDRESS_OPCODE_MAPPING.get(op, "INVALID")):
+        tact = 0
+    if watch is not None:
+        watch["nobj_peak"] = max(watch.get("nobj_peak", 0), lane.n_obj + lane.allocs)
     if not tact and _objects_full(lane, b.shape.obj_cap):
         b.status[i], b.aux[i] = MG_ESCAPE, op | (MG_ESC_TAINT << 8)
         return False
@@ -276,6 +294,11 @@ def step_lane(oracle, ops: np.ndarray, b, i: int, lane: RefLane, actions, hook_m
         b.rec_len[i] = rec0
         return False
     b.flags[i] = flags0
+    if int(b.status[i]) == MG_VMEXC:
+        # the mutator raised (gas, the stack limit, a pop past the stack's bottom): the
+        # step counts, the hooks' records and atoms are dropped with the state
+        b.rec_len[i] = rec0
+        return True
     if do_post:
         post_atom = lane.natoms + int(do_pre)
     _objects(b, i, lane, op, pc, sp, tact, pre_atom, post_atom, snap)
@@ -290,6 +313,8 @@ def step_lane(oracle, ops: np.ndarray, b, i: int, lane: RefLane, actions, hook_m
             lane.natoms += 1
             if tact & MG_TAINT_YCLASS:
                 lane.ymask.add(a)
+    if watch is not None and tact:
+        watch["actions"] = watch.get("actions", 0) + 1
     return True
 
 
@@ -300,12 +325,14 @@ def _objects(b, i, lane: RefLane, op, pc, sp0, tact, pre_atom, post_atom, snap):
     pre_k, sink_k = tact & 15, (tact >> 8) & 15
     if pre_atom is not None:
         st[sp0 - pre_k].ann.add(pre_atom)
+        lane.allocs += not st[sp0 - pre_k].tracked
         st[sp0 - pre_k].tracked = True
     if sink_k and sp0 >= sink_k:
         lane.sink |= st[sp0 - sink_k].ann
         lane.tflags |= 1
     before = [limbs_to_word(snap["stack"][s]) for s in range(max(0, sp0 - 3), sp0)][::-1]   # [-1], [-2], [-3]
     if 0x80 <= op <= 0x8F:                      # DUPn
+        lane.allocs += not st[-(op - 0x7F)].tracked
         st[-(op - 0x7F)].tracked = True
         st.append(st[-(op - 0x7F)])
     elif 0x90 <= op <= 0x9F:                    # SWAPn
@@ -331,14 +358,16 @@ def _objects(b, i, lane: RefLane, op, pc, sp0, tact, pre_atom, post_atom, snap):
                 r = Obj(popped[1].ann) if before[0] < 32 else Obj()
             else:
                 r = Obj()
+            lane.allocs += bool(r.ann) and op not in ENV_OPS
             st.append(r)
     if post_atom is not None:
         st[-1].ann.add(post_atom)
+        lane.allocs += not st[-1].tracked
         st[-1].tracked = True
 
 
 def run_lane(oracle, ops, b, i: int, actions, hook_mask, max_steps: int, max_depth: int, horizon: int,
-             loop_bound: int = 0, force=None) -> int:
+             loop_bound: int = 0, force=None, watch=None) -> int:
     """k_sym_step on one taint lane: steps until it stops or its budget ends.
     Returns instructions executed."""
     if int(b.status[i]) != MG_RUNNING:
@@ -358,7 +387,7 @@ def run_lane(oracle, ops, b, i: int, actions, hook_mask, max_steps: int, max_dep
             # whose pop is traced) can still stop the lane
             oracle.run(b, i, 1, hook_mask=hook_mask, max_steps=0, max_depth=max_depth, loop_bound=loop_bound)
             break
-        if not step_lane(oracle, ops, b, i, lane, actions, hook_mask, max_depth, acked, loop_bound, force):
+        if not step_lane(oracle, ops, b, i, lane, actions, hook_mask, max_depth, acked, loop_bound, force, watch):
             break
         executed += 1
     if executed and ack:

@@ -24,6 +24,7 @@ from mythril_amd.lanes import (MG_ENV_WORDS, MG_LANE_TAINT, MG_TAINT_OBJ0, LaneB
 from mythril_amd.laser import BreadthFirstSearchStrategy, DepthFirstSearchStrategy
 from mythril_amd.laser.opcodes import OPCODES
 from oracle_device import OracleDevice
+from taintdirect import partition as _partition
 
 pytestmark = pytest.mark.gpu
 
@@ -97,20 +98,6 @@ def _load(dev, b, codes, n_c2):
     b.code_id[:n_c2] = ids[0]
     for k in range(2 * len(CRAFTED)):
         b.code_id[n_c2 + k] = ids[1 + k // 2]
-
-
-def _partition(b, i):
-    """Per stack slot: (object class, atoms) with classes numbered by first
-    appearance; handle-0 slots are objects of their own."""
-    seen, out = {}, []
-    for s in range(int(b.sp[i])):
-        h = int(b.sobj[i, s])
-        key = ("fresh", s) if h == 0 else h
-        if key not in seen:
-            seen[key] = len(seen)
-        out.append((seen[key], int(b.omask[i, h]) if h else 0))
-    env = [int(b.omask[i, h]) for h in range(1, 7)]
-    return out, env
 
 
 @pytest.mark.parametrize("obj_cap", [64, 16])
