@@ -89,6 +89,9 @@ struct DevCode {
     uint32_t run_off[2]; // u32 [n_instr][2]         straight-line run from each instruction: [0] the run
                          //                          set with the environment pushes, [1] without (MG_K1_RUNENV=0)
     uint32_t fent_off;   // u8  [n_instr]            bit 0: index is a function entry, bit 1: index + 1 is
+    uint32_t dec_off;    // u32 [n_instr][2]         kernel 1's pre-decoded words of each instruction (gas;
+                         //                          opcode, counts, kind, flags), without the hook bit, which
+                         //                          a launch adds; 8-byte aligned, as the run tables are
 };
 
 // Per-launch statistics accumulated by the stepping kernel.

@@ -70,6 +70,10 @@ DEV void st_word(g_u4 *base, size_t idx, const U256 &v) {
 // of the block] (conflict-free at a common offset); HBM holds the rest, and the
 // window's bytes once the launch flushes them.  Solidity keeps its scratch words,
 // free-memory pointer and first allocation (0x00-0x9f) there.
+// Invariant: from the end of the kernel's prologue to its epilogue every dword of
+// a live lane's memory window at or beyond msize / 4 is zero (the prologue clears
+// the column before it fills [0, msize / 4) from HBM), so memory that grows inside
+// the window needs no zero fill: only the HBM part of a growth is cleared.
 // `ws` = lanes per block (the row stride), `tid` = the lane's index in its block.
 #define LANE_BLOCK 256u
 struct LaneView {
@@ -111,6 +115,10 @@ struct LaneView {
     DEV void set_gmdw(uint32_t dw, uint32_t v) const { gp(L.mem)[row(dw)] = v; }
     DEV uint32_t mdw(uint32_t dw) const { return dw < mw ? lmdw(dw) : gmdw(dw); }
     DEV uint32_t mdw_safe(uint32_t dw) const { return dw < L.mem_cap / 4u ? mdw(dw) : 0u; }
+    // Every writer extends msize over the bytes it writes before it calls this
+    // (MSTORE, MSTORE8, CALLDATACOPY, CODECOPY; an unaligned MSTORE's ninth dword
+    // still starts below msize; MLOAD, SHA3 and RETURN only read), so no store
+    // lands at or beyond msize / 4 and the window stays zero there.
     DEV void set_mdw(uint32_t dw, uint32_t v) const {
         if (dw < mw) set_lmdw(dw, v);
         else set_gmdw(dw, v);
@@ -196,6 +204,25 @@ DEV int mem_extend(const U256 &start, const U256 &size, uint32_t &msize, uint64_
     gmax += fee;
     msize = (uint32_t)(nw * 32u);
     return MX_OK;
+}
+
+// The fast loop's MLOAD / MSTORE: can the 32 bytes at `a` be accessed without the
+// general handler?  Yes inside msize (fee 0), and when the access grows memory to
+// `nms` bytes that still lie inside the LDS window and mem_cap (`grow_lim` =
+// min(4 * mw, mem_cap)): the window is zero past msize, so the growth is only the
+// fee of mem_extend above.  There nw <= 255, so the fee is exact in 32 bits.
+DEV bool mem_fast(const U256 &a, uint32_t msize, uint32_t grow_lim, uint32_t &nms, uint32_t &fee) {
+    nms = msize;
+    fee = 0u;
+    if (!u_fits32(a)) return false;
+    const uint32_t off = a.w[0];
+    if (msize >= 32u && off <= msize - 32u) return true;
+    if (off >= grow_lim) return false;                   // grow_lim <= 255 * 32: no wrap below
+    const uint32_t nw = (off + 63u) >> 5, ow = msize >> 5;
+    if (nw * 32u > grow_lim) return false;
+    nms = nw * 32u;
+    fee = 3u * (nw - ow) + (nw * nw) / 512u - (ow * ow) / 512u;
+    return true;
 }
 
 DEV bool gas_oog(uint64_t gmin, uint64_t txlim) { return gmin > MG_MSTATE_GAS_LIMIT || gmin >= txlim; }
@@ -434,7 +461,8 @@ __device__ __forceinline__ void slow_step(LaneRegs &R, const StepEnv &E, uint32_
 #define MEMX(st_, sz_, later_) { const int mx_ = mem_extend((st_), (sz_), nmsize, ngmin, ngmax, \
                                                         L.mem_cap, (later_), txlim); \
                                  if (mx_ == MX_OOG) EXCX(MG_EXC_OUT_OF_GAS) if (mx_ == MX_ESCAPE) ESCX(MG_ESC_MEMORY) }
-#define ZEROFILL() if (nmsize > msize0) V.mzero(msize0, nmsize);
+    // the window is zero past msize already (LaneView): clear the HBM part only
+#define ZEROFILL() if (nmsize > msize0) V.mzero(max(msize0, 4u * E.mw), nmsize);
 #define JUMP_OK(idx_) ((idx_) != MG_JRES_NONE && \
                        ((E.sflag && (idx_) < E.sn) ? (E.s_pd[(idx_)].y & 0xffu) : (uint32_t)gops[(idx_)]) == 0x5bu)
     // _new_node_state (svm.py:575-637): a JUMP / JUMPI successor at a function entry
@@ -817,7 +845,7 @@ DEV bool alu_is_fast(uint32_t op) { return op <= 0x03u || op == 0x0bu || (op >= 
 #define PD_NFENT (1u << 23)      // ... landing on the next instruction (JUMPI fall-through)
 #define PD_CREATION (1u << 29)   // escapes when the lane is a creation transaction
 #define PD_SPECIAL (1u << 30)    // kind >= K_ESCAPE (host opcode or past-the-end)
-DEV uint32_t pd_flags(uint32_t op, uint32_t dy, uint32_t hook) {
+__host__ DEV uint32_t pd_flags(uint32_t op, uint32_t dy, uint32_t hook) {   // host: mg_load_code
     const uint32_t kind = (dy >> 9) & 31u;
     return (hook << 31) | (kind >= K_ESCAPE ? PD_SPECIAL : 0u) | (op - 0x35u < 4u ? PD_CREATION : 0u);
 }
@@ -883,27 +911,45 @@ __device__ __noinline__ uint64_t trace_step(uint32_t *__restrict__ trace, size_t
 //   * the two top stack words live in registers, the next 14 in an LDS window,
 //     the rest in HBM;
 //   * common opcodes run inline; the rest (and any lane whose preconditions
-//     fail) go through slow_step, inlined too: the kernel uses no scratch.
+//     fail) go through slow_step, inlined too: the kernel uses no scratch;
+//   * the LDS memory window is zero past msize for the whole dispatch loop
+//     (LaneView), so MLOAD / MSTORE that grow memory inside it run inline and
+//     the general handlers zero only the HBM part of a growth;
+//   * the prologue is a short chain of device round trips: a lane reset from the
+//     resident image keeps the image's values in registers, the lane's own loads
+//     are issued before the staging barriers, and a block stages its code from
+//     the decode words mg_load_code wrote; the epilogue stores the counters it
+//     kept from the prologue instead of read-modify-writing them.
 // kLoop: BoundedLoopsStrategy traces on (a separate instantiation, so the common
 // case carries no trace call site in its loop)
 // Re-initialise one lane from the resident image (mg_lanes_reset): empty stack,
 // memory, traces and record logs; pc, depth, status, gas and storage from the image.
-__device__ __forceinline__ void reset_lane(const DevLanes &L, const DevResetImage &R, uint32_t lane) {
-    L.pc[lane] = R.pc[lane]; L.sp[lane] = 0; L.msize[lane] = 0; L.depth[lane] = R.depth[lane];
-    L.status[lane] = R.status[lane]; L.aux[lane] = R.aux[lane]; L.steps[lane] = R.steps[lane];
-    L.gas_min[lane] = R.gas_min[lane]; L.gas_max[lane] = R.gas_max[lane];
+// Returns what the stepping that follows needs of it, so the kernel does not read
+// its own stores back (sp, msize, the counters and the trace length are zero).
+struct LaneImage {
+    uint64_t gas_min, gas_max;
+    uint32_t pc, depth, status, steps;
+};
+__device__ __forceinline__ LaneImage reset_lane(const DevLanes &L, const DevResetImage &R, uint32_t lane) {
+    LaneImage I;
+    I.pc = R.pc[lane]; I.depth = R.depth[lane]; I.status = R.status[lane]; I.steps = R.steps[lane];
+    I.gas_min = R.gas_min[lane]; I.gas_max = R.gas_max[lane];
+    const uint32_t aux = R.aux[lane], cnt = R.storage_count[lane];
+    L.pc[lane] = I.pc; L.sp[lane] = 0; L.msize[lane] = 0; L.depth[lane] = I.depth;
+    L.status[lane] = I.status; L.aux[lane] = aux; L.steps[lane] = I.steps;
+    L.gas_min[lane] = I.gas_min; L.gas_max[lane] = I.gas_max;
     L.sha3_count[lane] = 0; L.exp_count[lane] = 0;
     L.trace_len[lane] = 0;                 // reset images start with empty traces
     L.rec_len[lane] = 0;                   // ... and empty record logs
     L.fent[lane] = MG_FENT_NONE;           // ... and no function switch yet
-    const uint32_t cnt = R.storage_count[lane];
     L.storage_count[lane] = cnt;
-    for (uint32_t s = 0; s < cnt; ++s)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const size_t idx = ((size_t)s * L.N + lane) * 4 + k;
-            L.storage[idx] = R.storage[idx];
-        }
+    for (uint32_t s = 0; s < cnt; ++s) {
+        const size_t idx = ((size_t)s * L.N + lane) * 4;
+        // one entry's four loads in flight together
+        const uint4 e0 = R.storage[idx], e1 = R.storage[idx + 1], e2 = R.storage[idx + 2], e3 = R.storage[idx + 3];
+        L.storage[idx] = e0; L.storage[idx + 1] = e1; L.storage[idx + 2] = e2; L.storage[idx + 3] = e3;
+    }
+    return I;
 }
 
 // The lane constant an environment opcode of the run set pushes (run_table.h
@@ -1003,11 +1049,48 @@ __global__ __launch_bounds__(LANE_BLOCK) void k_lane_step(DevLanes L, const DevC
     const uint32_t tid = (threadIdx.x >> 6) * lpw + wlane;     // lane index in the block
     const uint32_t lane = blockIdx.x * lanes_pb + tid;
     const bool in_range = wlane < lpw && lane < L.n;
-    // mg_run_batches: re-initialise the lane from the resident image first (the
-    // reads below see this thread's own stores)
-    if (R.pc != nullptr && in_range) reset_lane(L, R, lane);
-    uint32_t status = in_range ? L.status[lane] : MG_HALT_STOP;
-    const uint32_t my_code = in_range ? L.code_id[lane] : 0u;
+    const LaneView V{L, lane, s_win, win, tid, lanes_pb, s_mw, mw};
+    // The lane's memory-window column starts out zero (LaneView's invariant; the
+    // fill below overwrites [0, msize / 4)).  LDS stores that nothing waits on,
+    // issued ahead of the prologue's device loads.
+    if (wlane < lpw)
+        for (uint32_t k = 0; k < mw; ++k) V.set_lmdw(k, 0u);
+    // mg_run_batches: re-initialise the lane from the resident image first; what
+    // the image gave stays in registers (no read-back of this thread's stores)
+    const bool from_image = R.pc != nullptr;
+    LaneImage I{};
+    uint32_t status = MG_HALT_STOP, my_code = 0u;
+    if (in_range) {
+        my_code = L.code_id[lane];
+        if (from_image) { I = reset_lane(L, R, lane); status = I.status; }
+        else status = L.status[lane];
+    }
+    // The lane's own loads, issued here so that their latency overlaps the
+    // staging below: code descriptor, flags, gas limit and, when the lane was not
+    // reset a moment ago, its scalars.
+    const bool run_st = in_range && status == MG_RUNNING;
+    DevCode C{};
+    uint32_t flags = 0, pc = 0, sp = 0, msize = 0, depth = 0, aux = 0, n_sha3 = 0, n_exp = 0;
+    uint32_t tlen = 0;                                    // trace length (BoundedLoops)
+    uint32_t fent = MG_FENT_NONE;                         // last function-entry landing
+    uint32_t steps0 = 0;                                  // L.steps at entry
+    const uint32_t loop_on = kLoop ? loop_bound : 0u;     // kernel argument: uniform
+    uint64_t txlim = 0, gmin = 0, gmax = 0;
+    if (run_st) {
+        C = codes[my_code];
+        flags = L.flags[lane];
+        txlim = L.gas_limit[lane];
+        if (from_image) {
+            pc = I.pc; depth = I.depth; gmin = I.gas_min; gmax = I.gas_max; steps0 = I.steps;
+        } else {
+            pc = L.pc[lane]; sp = L.sp[lane]; msize = L.msize[lane]; depth = L.depth[lane];
+            fent = L.fent[lane];
+            if (loop_on) tlen = L.trace_len[lane];
+            gmin = L.gas_min[lane]; gmax = L.gas_max[lane];
+            // the counters are kept absolute: the epilogue stores them, no read-modify-write
+            steps0 = L.steps[lane]; n_sha3 = L.sha3_count[lane]; n_exp = L.exp_count[lane];
+        }
+    }
     for (uint32_t i = threadIdx.x; i < 256u; i += blockDim.x) s_dec[i] = kDec[i];
     if (prof)
         for (uint32_t i = threadIdx.x; i < 260u; i += blockDim.x) s_prof[i] = 0u;
@@ -1038,22 +1121,24 @@ __global__ __launch_bounds__(LANE_BLOCK) void k_lane_step(DevLanes L, const DevC
     const uint32_t bcode = s_code;
     const bool mixed = __syncthreads_or(status == MG_RUNNING && my_code != bcode);
     bool staged = false, jstaged = false;
-    uint32_t ns_b = 0u, sn_b = 0u, jn_b = 0u, push_b = 0u;
+    uint32_t ns_b = 0u, sn_b = 0u, jn_b = 0u, push_b = 0u, cov_b = 0u;
     if (bcode != 0xffffffffu && !mixed) {
         const DevCode BC = codes[bcode];
         const uint32_t ns = min(BC.n_instr, pd_cap - 1u);   // staged prefix
         if (ns > 0u) {
             // run table variant (selected, not indexed: a dynamic index would put BC in scratch)
             const uint32_t run_off = (lpw_flags & K1_NO_RUNENV) ? BC.run_off[1] : BC.run_off[0];
-            // pre-decode: opcode, gas, stack counts, kind, and the hook bit (bit 31)
+            // pre-decode: the code's load-time decode words (opcode, gas, stack counts,
+            // kind, flags: mg_load_code) and its run entry, two independent 8-byte
+            // loads, plus this launch's hook bit (bit 31) for the opcode in y
+            const uint2 *__restrict__ gdec = reinterpret_cast<const uint2 *>(a32 + BC.dec_off);
+            const uint2 *__restrict__ grun = reinterpret_cast<const uint2 *>(a32 + run_off);
             for (uint32_t i = threadIdx.x; i < ns; i += blockDim.x) {
-                const uint32_t op = a8[BC.op_off + i];
-                const uint2 d = kDec[op];
+                const uint2 d = gdec[i], r = grun[i];
+                const uint32_t op = d.y & 0xffu;
                 const uint64_t hm = op < 64u ? m0 : op < 128u ? m1 : op < 192u ? m2 : m3;
                 const uint32_t hook = (uint32_t)((hm >> (op & 63u)) & 1ull);
-                s_pd[i] = make_uint4(d.x, op | (d.y << 8) | pd_flags(op, d.y, hook) |
-                                              ((uint32_t)a8[BC.fent_off + i] << 22),
-                                     a32[run_off + 2u * i], a32[run_off + 2u * i + 1u]);
+                s_pd[i] = make_uint4(d.x, d.y | (hook << 31), r.x, r.y);
                 s_cov[i] = 0;
             }
             if (threadIdx.x == 0 && ns == BC.n_instr)
@@ -1066,6 +1151,7 @@ __global__ __launch_bounds__(LANE_BLOCK) void k_lane_step(DevLanes L, const DevC
             ns_b = ns;
             sn_b = ns == BC.n_instr ? ns + 1u : ns;
             push_b = BC.push_off;
+            cov_b = BC.cov_off;
             const uint32_t jn = min(BC.n_jres, jr_cap);
             if (jn > 0u && BC.n_instr < 0xffffu) {
                 for (uint32_t i = threadIdx.x; i < jn; i += blockDim.x) {
@@ -1080,8 +1166,8 @@ __global__ __launch_bounds__(LANE_BLOCK) void k_lane_step(DevLanes L, const DevC
     }
     uint32_t executed = 0;
     // symbolic and taint lanes (MG_LANE_SYMBOLIC, MG_LANE_TAINT) are k_sym_step's: counted as running, untouched
-    const bool sym_lane = in_range && status == MG_RUNNING && (L.flags[lane] & (16u | 2048u)) != 0u;
-    const bool run0 = status == MG_RUNNING && !sym_lane;
+    const bool sym_lane = run_st && (flags & (16u | 2048u)) != 0u;
+    const bool run0 = run_st && !sym_lane;
     // block-uniform facts in scalar registers
     const uint32_t sflag = __builtin_amdgcn_readfirstlane(staged ? 1u : 0u);
     const uint32_t jflag = __builtin_amdgcn_readfirstlane(jstaged ? 1u : 0u);
@@ -1089,33 +1175,25 @@ __global__ __launch_bounds__(LANE_BLOCK) void k_lane_step(DevLanes L, const DevC
     const uint32_t sn = __builtin_amdgcn_readfirstlane(sn_b);     // + the END sentinel
     const uint32_t jn = __builtin_amdgcn_readfirstlane(jn_b);     // staged jump targets
     const uint32_t bpush = __builtin_amdgcn_readfirstlane(push_b);
+    const uint32_t bcov = __builtin_amdgcn_readfirstlane(cov_b);  // the staged code's coverage bytes
     const uint32_t psflag = (staged && push_lds) ? 1u : 0u;
     // push immediate of instruction i of the staged code (wave-uniform i in runs)
 #define PUSH_IMM(i_) (psflag ? ld_word((const l_u4 *)s_push, (i_)) : ld_word(gv(a32 + bpush), (i_)))
     const uint32_t stack_lim = L.stack_cap < MG_STACK_LIMIT ? L.stack_cap : MG_STACK_LIMIT;
 
     // ---- per-lane machine state (registers) ----
-    const LaneView V{L, lane, s_win, win, tid, lanes_pb, s_mw, mw};
-    DevCode C{};
-    uint32_t flags = 0, pc = 0, sp = 0, msize = 0, depth = 0, aux = 0, n_sha3 = 0, n_exp = 0;
-    uint32_t tlen = 0;                                    // trace length (BoundedLoops)
-    uint32_t fent = MG_FENT_NONE;                         // last function-entry landing
-    const uint32_t loop_on = kLoop ? loop_bound : 0u;     // kernel argument: uniform
-    uint64_t txlim = 0, glim = 0, gmin = 0, gmax = 0;
+    // (loaded before the staging; a symbolic or taint lane's values go unused)
+    if (!run0) flags = 0u;
+    uint64_t glim = 0;
     U256 T0 = u_zero(), T1 = u_zero();
     uint2 pd = make_uint2(0u, 0u);
     uint2 prun = make_uint2(0u, 0u);   // run table entry at pc (staged code only)
     bool live = false;
+    // the inline MLOAD / MSTORE grow memory up to here (mem_fast)
+    const uint32_t grow_lim = min(4u * mw, L.mem_cap);
     if (run0) {
-        C = codes[my_code];
-        flags = L.flags[lane];
-        txlim = L.gas_limit[lane];
         // accumulate_gas OOG test (instructions.py:162-176): min > 1e9 or min >= tx gas limit
         glim = txlim < MG_MSTATE_GAS_LIMIT + 1ull ? txlim : MG_MSTATE_GAS_LIMIT + 1ull;
-        pc = L.pc[lane]; sp = L.sp[lane]; msize = L.msize[lane]; depth = L.depth[lane];
-        fent = L.fent[lane];
-        if (loop_on) tlen = L.trace_len[lane];
-        gmin = L.gas_min[lane]; gmax = L.gas_max[lane];
         for (uint32_t k = 0; k < min(sp, win); ++k) V.set_wstack(k, V.gstack(k));   // window fill
         for (uint32_t k = 0; k < min(msize >> 2, mw); ++k) V.set_lmdw(k, V.gmdw(k));
         if (sp >= 1u) T0 = V.stack(sp - 1u);
@@ -1128,10 +1206,7 @@ __global__ __launch_bounds__(LANE_BLOCK) void k_lane_step(DevLanes L, const DevC
     const bool hook_ack = (flags & MG_LANE_HOOK_ACK) != 0u;
     uint32_t lane_max = (flags & MG_LANE_STEP1) ? min(max_steps, 1u) : max_steps;
     // step horizon (mg_step_until): the lane pauses once its cumulative steps reach it
-    if (horizon && run0) {
-        const uint32_t s0 = L.steps[lane];
-        lane_max = min(lane_max, horizon > s0 ? horizon - s0 : 0u);
-    }
+    if (horizon && run0) lane_max = min(lane_max, horizon > steps0 ? horizon - steps0 : 0u);
     const uint8_t *__restrict__ gops = a8 + C.op_off;
     const uint8_t *__restrict__ gfent = a8 + C.fent_off;
     const StepEnv E{&L, C, a8, a32, s_win, s_mw, s_pd, s_push, s_prof, s_kc + (threadIdx.x >> 6) * KC_WAVE,
@@ -1536,19 +1611,33 @@ __global__ __launch_bounds__(LANE_BLOCK) void k_lane_step(DevLanes L, const DevC
                 PUSHV(r);
             }
             break;
-        case K_MLOAD:                   // inside msize: no extension, table gas only
-            ok = gas_ok && sp >= 1u && u_fits32(T0) && msize >= 32u && T0.w[0] <= msize - 32u;
-            if (ok) { T0 = V.mword(T0.w[0]); ++pc; gmin = ngmin; gmax = ngmax; }
-            break;
-        case K_MSTORE:
-            ok = gas_ok && sp >= 2u && u_fits32(T0) && msize >= 32u && T0.w[0] <= msize - 32u;
+        // MLOAD / MSTORE inside msize (table gas only) or growing memory inside the
+        // window (mem_fast), with the general path's checks in its order: mem_extend's
+        // gmin + fee <= the machine-state limit, then GASCOMMIT's + table gas < glim
+        case K_MLOAD: {
+            uint32_t nms, fee;
+            ok = sp >= 1u && mem_fast(T0, msize, grow_lim, nms, fee) &&
+                 gmin + fee <= MG_MSTATE_GAS_LIMIT && ngmin + fee < glim;
             if (ok) {
+                msize = nms;
+                T0 = V.mword(T0.w[0]);
+                ++pc; gmin = ngmin + fee; gmax = ngmax + fee;
+            }
+            break;
+        }
+        case K_MSTORE: {
+            uint32_t nms, fee;
+            ok = sp >= 2u && mem_fast(T0, msize, grow_lim, nms, fee) &&
+                 gmin + fee <= MG_MSTATE_GAS_LIMIT && ngmin + fee < glim;
+            if (ok) {
+                msize = nms;
                 V.set_mword(T0.w[0], T1);
                 T0 = sp >= 3u ? V.stack(sp - 3u) : u_zero();
                 T1 = sp >= 4u ? V.stack(sp - 4u) : u_zero();
-                sp -= 2u; ++pc; gmin = ngmin; gmax = ngmax;
+                sp -= 2u; ++pc; gmin = ngmin + fee; gmax = ngmax + fee;
             }
             break;
+        }
         case K_CDLOAD: {                // aligned and inside the calldata
             const uint32_t cdl = L.calldata_len[lane];
             ok = gas_ok && sp >= 1u && u_fits32(T0) && (T0.w[0] & 3u) == 0u &&
@@ -1607,9 +1696,10 @@ __global__ __launch_bounds__(LANE_BLOCK) void k_lane_step(DevLanes L, const DevC
         if (loop_on) L.trace_len[lane] = tlen;
         // HOOK_ACK covers one instruction: consumed once the lane has executed
         if (hook_ack && executed > 0u) L.flags[lane] = flags & ~MG_LANE_HOOK_ACK;
-        L.steps[lane] += executed;
-        if (n_sha3) L.sha3_count[lane] += n_sha3;
-        if (n_exp) L.exp_count[lane] += n_exp;
+        // plain stores: the prologue kept the counters' values at entry
+        L.steps[lane] = steps0 + executed;
+        L.sha3_count[lane] = n_sha3;
+        L.exp_count[lane] = n_exp;
     }
 
 #ifdef MG_K1_CLOCKS
@@ -1623,9 +1713,8 @@ __global__ __launch_bounds__(LANE_BLOCK) void k_lane_step(DevLanes L, const DevC
 #undef CLK_MARK
     if (staged && cov_on) {
         __syncthreads();
-        const DevCode BC = codes[bcode];
         for (uint32_t i = threadIdx.x; i < ns; i += blockDim.x)
-            if (s_cov[i]) cov[BC.cov_off + i] = 1;
+            if (s_cov[i]) cov[bcov + i] = 1;
     }
     if (prof) {
         __syncthreads();

@@ -422,11 +422,23 @@ extern "C" int mg_load_code(mg_ctx *ctx, const uint8_t *code, size_t n, uint32_t
         const size_t ni = ops.size();
         uint32_t gt0[256], gt1[256];
         for (int b = 0; b < 256; ++b) { gt0[b] = t[b].gmin; gt1[b] = t[b].gmax; }
+        if (ctx->a32.size() % 2) ctx->a32.push_back(0);      // pairs read as one 8-byte load
         for (int v = 0; v < 2; ++v) {
             std::vector<uint32_t> rx, ry;
             runtab::run_table(ops.data(), ni, gt0, gt1, v == 0, rx, ry);
             dc.run_off[v] = (uint32_t)ctx->a32.size();
             for (size_t i = 0; i < ni; ++i) { ctx->a32.push_back(rx[i]); ctx->a32.push_back(ry[i]); }
+        }
+        // kernel 1's pre-decoded words (lane_step.cuh s_pd x, y), which depend on the
+        // code alone: x = the table gas, y = op | decode y << 8 | flags | entry bits
+        // << 22.  The launch's hook bit (bit 31) is ORed in when a block stages them.
+        uint2 dec[256];
+        build_decode(dec);
+        dc.dec_off = (uint32_t)ctx->a32.size();
+        for (size_t i = 0; i < ni; ++i) {
+            const uint32_t op = ops[i];
+            ctx->a32.push_back(dec[op].x);
+            ctx->a32.push_back(op | (dec[op].y << 8) | pd_flags(op, dec[op].y, 0u) | ((uint32_t)fent[i] << 22));
         }
     }
     dc.cov_off = ctx->cov_total;
