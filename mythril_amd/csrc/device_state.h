@@ -68,11 +68,13 @@ struct DevTaint {
 
 // Resident initial image of a batch (mg_lanes_reset); passed to the stepping
 // kernel when it re-initialises every lane itself before stepping
-// (mg_run_batches), pc == nullptr otherwise.
+// (mg_run_batches), pc == nullptr otherwise.  The kernels only read it; the
+// pointers are not const because the context keeps this struct and every
+// upload writes the planes (the second destination of these fields).
 struct DevResetImage {
-    const uint32_t *pc, *depth, *status, *aux, *steps, *storage_count;
-    const uint64_t *gas_min, *gas_max;
-    const uint4 *storage;
+    uint32_t *pc, *depth, *status, *aux, *steps, *storage_count;
+    uint64_t *gas_min, *gas_max;
+    uint4 *storage;
 };
 
 // One loaded code (Disassembly): arrays live in one device arena.

@@ -66,11 +66,7 @@ struct mg_ctx {
     uint8_t *d_tforce = nullptr;         // per code instruction (coverage layout): host-run hooks
     size_t cap_tforce = 0;
     std::vector<void *> lane_allocs;
-    // resident initial image for mg_lanes_reset
-    uint32_t *i_pc = nullptr, *i_depth = nullptr, *i_status = nullptr, *i_aux = nullptr,
-             *i_steps = nullptr, *i_storage_count = nullptr;
-    uint64_t *i_gas_min = nullptr, *i_gas_max = nullptr;
-    uint4 *i_storage = nullptr;
+    DevResetImage RI{};                  // resident initial image for mg_lanes_reset, freed with the lanes
     // staging for upload/download (lane-major)
     void *d_stage = nullptr;
     size_t stage_bytes = 0;
@@ -249,6 +245,7 @@ static void free_lanes(mg_ctx *ctx) {
     ctx->lane_allocs.clear();
     ctx->have_lanes = ctx->uploaded = false;
     ctx->L = DevLanes{};
+    ctx->RI = DevResetImage{};
     ctx->S = DevSym{};
     ctx->T = DevTaint{};
     ctx->E = DevExplore{};
@@ -495,13 +492,15 @@ extern "C" int mg_code_table(mg_ctx *ctx, uint32_t code_id, uint8_t *ops, uint32
 }
 
 // ------------------------------------------------------------------- lanes
+// every plane of a batch: freed by free_lanes; zero: cleared on the context's stream
 template <class T>
-static int lane_alloc(mg_ctx *ctx, T *&p, size_t count) {
+static int lane_alloc(mg_ctx *ctx, T *&p, size_t count, bool zero = false) {
+    const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
     void *q = nullptr;
-    if (hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess)
-        return set_err(ctx, MG_ENOMEM, "hipMalloc %zu bytes for lanes", count * sizeof(T));
+    if (hipMalloc(&q, bytes) != hipSuccess) return set_err(ctx, MG_ENOMEM, "hipMalloc %zu bytes for lanes", bytes);
     ctx->lane_allocs.push_back(q);
     p = (T *)q;
+    if (zero) HIPX(ctx, hipMemsetAsync(q, 0, bytes, ctx->stream));
     return MG_OK;
 }
 
@@ -516,6 +515,7 @@ extern "C" int mg_lanes_alloc(mg_ctx *ctx, const mg_batch_cfg *cfg) {
     ctx->code_used.assign(ctx->codes.size(), 0);
     ctx->cfg = *cfg;
     DevLanes &L = ctx->L;
+    DevResetImage &RI = ctx->RI;
     L.n = cfg->n_lanes;
     L.N = (cfg->n_lanes + 63u) & ~63u;
     L.stack_cap = cfg->stack_cap; L.mem_cap = cfg->mem_cap;
@@ -524,11 +524,11 @@ extern "C" int mg_lanes_alloc(mg_ctx *ctx, const mg_batch_cfg *cfg) {
     int rc = 0;
     uint32_t **u32s[] = {&L.code_id, &L.pc, &L.sp, &L.msize, &L.depth, &L.status, &L.aux, &L.steps,
                          &L.flags, &L.calldata_len, &L.storage_count, &L.ret_offset, &L.ret_len,
-                         &L.sha3_count, &L.exp_count, &L.fent, &ctx->i_pc, &ctx->i_depth, &ctx->i_status,
-                         &ctx->i_aux, &ctx->i_steps, &ctx->i_storage_count};
+                         &L.sha3_count, &L.exp_count, &L.fent, &RI.pc, &RI.depth, &RI.status,
+                         &RI.aux, &RI.steps, &RI.storage_count};
     for (auto pp : u32s)
         if ((rc = lane_alloc(ctx, *pp, N))) return rc;
-    uint64_t **u64s[] = {&L.gas_min, &L.gas_max, &L.gas_limit, &ctx->i_gas_min, &ctx->i_gas_max};
+    uint64_t **u64s[] = {&L.gas_min, &L.gas_max, &L.gas_limit, &RI.gas_min, &RI.gas_max};
     for (auto pp : u64s)
         if ((rc = lane_alloc(ctx, *pp, N))) return rc;
     if ((rc = lane_alloc(ctx, L.stack, (size_t)L.stack_cap * N * 2))) return rc;
@@ -536,7 +536,7 @@ extern "C" int mg_lanes_alloc(mg_ctx *ctx, const mg_batch_cfg *cfg) {
     if ((rc = lane_alloc(ctx, L.calldata, (size_t)(L.calldata_cap / 4) * N))) return rc;
     if ((rc = lane_alloc(ctx, L.env, (size_t)MG_ENV_WORDS * N * 2))) return rc;
     if ((rc = lane_alloc(ctx, L.storage, (size_t)L.storage_cap * N * 4))) return rc;
-    if ((rc = lane_alloc(ctx, ctx->i_storage, (size_t)L.storage_cap * N * 4))) return rc;
+    if ((rc = lane_alloc(ctx, RI.storage, (size_t)L.storage_cap * N * 4))) return rc;
     L.trace_cap = cfg->trace_cap;
     if ((rc = lane_alloc(ctx, L.trace_len, N))) return rc;
     if (L.trace_cap && (rc = lane_alloc(ctx, L.trace, (size_t)L.trace_cap * N))) return rc;
@@ -841,16 +841,65 @@ static int xfer_up(mg_ctx *ctx, const XferPlan &x) {
     return MG_OK;
 }
 
+// the host image's capacities against the batch's (h is not null)
+static int check_host_caps(mg_ctx *ctx, const mg_lane_soa *h) {
+    const DevLanes &L = ctx->L;
+    if (h->stack_cap > L.stack_cap || h->mem_cap > L.mem_cap || h->mem_cap % 4 || h->calldata_cap > L.calldata_cap ||
+        h->calldata_cap % 4 || h->storage_cap > L.storage_cap || h->trace_cap > L.trace_cap || h->rec_cap > L.rec_cap)
+        return set_err(ctx, MG_EINVAL, "host image capacities exceed the batch configuration");
+    return MG_OK;
+}
+
 static int check_host_shape(mg_ctx *ctx, const mg_lane_soa *h, uint32_t first, uint32_t n) {
     if (!ctx->have_lanes) return set_err(ctx, MG_ESTATE, "mg_lanes_alloc first");
     if (!h || h->n != n || first + (uint64_t)n > ctx->L.n)
         return set_err(ctx, MG_EINVAL, "lane range [%u,%u) outside batch of %u (host n=%u)", first,
                        first + n, ctx->L.n, h ? h->n : 0);
-    if (h->stack_cap > ctx->L.stack_cap || h->mem_cap > ctx->L.mem_cap || h->mem_cap % 4 ||
-        h->calldata_cap > ctx->L.calldata_cap || h->calldata_cap % 4 || h->storage_cap > ctx->L.storage_cap ||
-        h->trace_cap > ctx->L.trace_cap || h->rec_cap > ctx->L.rec_cap)
-        return set_err(ctx, MG_EINVAL, "host image capacities exceed the batch configuration");
-    return MG_OK;
+    return check_host_caps(ctx, h);
+}
+
+// ---- the lane planes, each named once: every transfer of them is built here.
+// The per-lane scalars; I (upload only) is the reset image, the second destination
+// of the fields that mg_lanes_reset restores.
+static void plan_lane_scalars(XferPlan &x, const mg_lane_soa *h, const DevLanes &L, const DevResetImage *I) {
+    x.scalar(h->code_id, L.code_id, 4);
+    x.scalar(h->pc, L.pc, 4, I ? I->pc : nullptr);
+    x.scalar(h->sp, L.sp, 4);
+    x.scalar(h->msize, L.msize, 4);
+    x.scalar(h->depth, L.depth, 4, I ? I->depth : nullptr);
+    x.scalar(h->status, L.status, 4, I ? I->status : nullptr);
+    x.scalar(h->aux, L.aux, 4, I ? I->aux : nullptr);
+    x.scalar(h->steps, L.steps, 4, I ? I->steps : nullptr);
+    x.scalar(h->flags, L.flags, 4);
+    x.scalar(h->calldata_len, L.calldata_len, 4);
+    x.scalar(h->storage_count, L.storage_count, 4, I ? I->storage_count : nullptr);
+    x.scalar(h->ret_offset, L.ret_offset, 4);
+    x.scalar(h->ret_len, L.ret_len, 4);
+    x.scalar(h->gas_min, L.gas_min, 8, I ? I->gas_min : nullptr);
+    x.scalar(h->gas_max, L.gas_max, 8, I ? I->gas_max : nullptr);
+    x.scalar(h->gas_limit, L.gas_limit, 8);
+    if (h->trace_cap) x.scalar(h->trace_len, L.trace_len, 4);
+    if (h->rec_cap) x.scalar(h->rec_len, L.rec_len, 4);
+    if (h->fent) x.scalar(h->fent, L.fent, 4);
+}
+
+// How much of each row field a transfer moves, in units (XferPlan clips to the host
+// capacity); env and calldata have no count and go whole or not at all.
+struct LaneBounds {
+    uint32_t stack, mem_dwords, storage, trace, rec;
+    bool whole_inputs;
+};
+static const uint32_t XB_ALL = 0xffffffffu;
+
+static void plan_lane_rows(XferPlan &x, const mg_lane_soa *h, const DevLanes &L, const LaneBounds &b,
+                           const DevResetImage *I) {
+    x.units(h->stack, h->stack_cap, 8, L.stack, b.stack);
+    if (b.whole_inputs) x.units(h->env, MG_ENV_WORDS, 8, L.env);
+    x.units(h->storage, h->storage_cap, 16, L.storage, b.storage, I ? I->storage : nullptr);
+    x.bytes(h->memory, h->mem_cap, L.mem, b.mem_dwords);
+    if (b.whole_inputs) x.bytes(h->calldata, h->calldata_cap, L.calldata);
+    x.units(h->trace, h->trace_cap, 1, L.trace, b.trace);     // a capacity of 0 adds nothing
+    x.units(h->rec, h->rec_cap, 1, L.rec, b.rec);
 }
 
 static int lanes_upload(mg_ctx *ctx, const mg_lane_soa *h, uint32_t first, uint32_t n);
@@ -885,42 +934,17 @@ static int lanes_upload(mg_ctx *ctx, const mg_lane_soa *h, uint32_t first, uint3
     for (uint32_t i = 0; i < n && fresh; ++i)
         fresh = h->sp[i] == 0 && h->msize[i] == 0 && (!h->trace_cap || h->trace_len[i] == 0) &&
                 (!h->rec_cap || h->rec_len[i] == 0);
-    XferPlan x(n, first);
-    x.scalar(h->code_id, L.code_id, 4);
-    x.scalar(h->pc, L.pc, 4, ctx->i_pc);
-    x.scalar(h->sp, L.sp, 4);
-    x.scalar(h->msize, L.msize, 4);
-    x.scalar(h->depth, L.depth, 4, ctx->i_depth);
-    x.scalar(h->status, L.status, 4, ctx->i_status);
-    x.scalar(h->aux, L.aux, 4, ctx->i_aux);
-    x.scalar(h->steps, L.steps, 4, ctx->i_steps);
-    x.scalar(h->flags, L.flags, 4);
-    x.scalar(h->calldata_len, L.calldata_len, 4);
-    x.scalar(h->storage_count, L.storage_count, 4, ctx->i_storage_count);
-    x.scalar(h->ret_offset, L.ret_offset, 4);
-    x.scalar(h->ret_len, L.ret_len, 4);
-    x.scalar(h->gas_min, L.gas_min, 8, ctx->i_gas_min);
-    x.scalar(h->gas_max, L.gas_max, 8, ctx->i_gas_max);
-    x.scalar(h->gas_limit, L.gas_limit, 8);
-    if (h->fent) x.scalar(h->fent, L.fent, 4);
     // rows below the range's largest sp / storage count / msize / trace and record
     // length: no step reads above them before writing (pushes write their slot,
     // stores and logs append, memory is zero-filled when it extends), so the rest
     // of each capacity never crosses PCIe and the device rows above the bounds keep
     // their contents; env and calldata go whole (a step reads any byte of them)
-    x.units(h->stack, h->stack_cap, 8, L.stack, max_of(h->sp, n));
-    x.units(h->env, MG_ENV_WORDS, 8, L.env);
-    x.units(h->storage, h->storage_cap, 16, L.storage, max_of(h->storage_count, n), ctx->i_storage);
-    x.bytes(h->memory, h->mem_cap, L.mem, (max_of(h->msize, n) + 3u) / 4u);
-    x.bytes(h->calldata, h->calldata_cap, L.calldata);
-    if (h->trace_cap) {
-        x.scalar(h->trace_len, L.trace_len, 4);
-        x.units(h->trace, h->trace_cap, 1, L.trace, max_of(h->trace_len, n));
-    }
-    if (h->rec_cap) {
-        x.scalar(h->rec_len, L.rec_len, 4);
-        x.units(h->rec, h->rec_cap, 1, L.rec, max_of(h->rec_len, n));
-    }
+    const LaneBounds b{max_of(h->sp, n), (max_of(h->msize, n) + 3u) / 4u, max_of(h->storage_count, n),
+                       h->trace_cap ? max_of(h->trace_len, n) : 0u, h->rec_cap ? max_of(h->rec_len, n) : 0u, true};
+    XferPlan x(n, first);
+    plan_lane_scalars(x, h, L, &ctx->RI);
+    plan_lane_rows(x, h, L, b, &ctx->RI);
+    // what the host does not supply starts clean
     HIPX(ctx, hipMemsetAsync(L.sha3_count + first, 0, (size_t)n * 4, ctx->stream));
     HIPX(ctx, hipMemsetAsync(L.exp_count + first, 0, (size_t)n * 4, ctx->stream));
     if (!h->trace_cap) HIPX(ctx, hipMemsetAsync(L.trace_len + first, 0, (size_t)n * 4, ctx->stream));
@@ -945,22 +969,25 @@ extern "C" int mg_sym_alloc(mg_ctx *ctx, uint32_t node_cap, uint32_t const_cap) 
     S.node_cap = node_cap;
     S.const_cap = const_cap;
     const size_t N = ctx->L.N;
-    auto get = [&](void **p, size_t bytes) -> int {
-        if (hipMalloc(p, bytes) != hipSuccess) return set_err(ctx, MG_ENOMEM, "mg_sym_alloc: %zu bytes", bytes);
-        ctx->lane_allocs.push_back(*p);
-        return hipMemsetAsync(*p, 0, bytes, ctx->stream) == hipSuccess ? MG_OK : MG_EDEVICE;
-    };
-    int rc;
-    if ((rc = get((void **)&S.stag, (size_t)ctx->L.stack_cap * N * 4))) return rc;
-    if ((rc = get((void **)&S.node, (size_t)node_cap * N * 16))) return rc;
-    if ((rc = get((void **)&S.cval, (size_t)const_cap * N * 32))) return rc;
-    if ((rc = get((void **)&S.n_nodes, N * 4))) return rc;
-    if ((rc = get((void **)&S.n_consts, N * 4))) return rc;
-    if ((rc = get((void **)&S.mtag, (size_t)ctx->L.mem_cap * N * 4))) return rc;
-    if ((rc = get((void **)&S.sttag, (size_t)ctx->L.storage_cap * N * 8))) return rc;
+    int rc;                             // every plane zeroed (the uint4 planes count 16-byte elements)
+    if ((rc = lane_alloc(ctx, S.stag, (size_t)ctx->L.stack_cap * N, true))) return rc;
+    if ((rc = lane_alloc(ctx, S.node, (size_t)node_cap * N, true))) return rc;
+    if ((rc = lane_alloc(ctx, S.cval, (size_t)const_cap * N * 2, true))) return rc;
+    if ((rc = lane_alloc(ctx, S.n_nodes, N, true))) return rc;
+    if ((rc = lane_alloc(ctx, S.n_consts, N, true))) return rc;
+    if ((rc = lane_alloc(ctx, S.mtag, (size_t)ctx->L.mem_cap * N, true))) return rc;
+    if ((rc = lane_alloc(ctx, S.sttag, (size_t)ctx->L.storage_cap * N, true))) return rc;
     HIPX(ctx, hipStreamSynchronize(ctx->stream));
     ctx->S = S;
     ctx->hv_valid = false;
+    return MG_OK;
+}
+
+// the symbolic host image's capacities against the allocation (h is not null)
+static int check_sym_caps(mg_ctx *ctx, const mg_sym_soa *h) {
+    if (h->stack_cap > ctx->L.stack_cap || h->node_cap > ctx->S.node_cap || h->const_cap > ctx->S.const_cap ||
+        h->mem_cap > ctx->L.mem_cap || h->storage_cap > ctx->L.storage_cap)
+        return set_err(ctx, MG_EINVAL, "symbolic host image capacities exceed the allocation");
     return MG_OK;
 }
 
@@ -968,10 +995,32 @@ static int check_sym_shape(mg_ctx *ctx, const mg_sym_soa *h, uint32_t first, uin
     if (!ctx->S.node) return set_err(ctx, MG_ESTATE, "mg_sym_alloc first");
     if (!h || h->n != n || first + (uint64_t)n > ctx->L.n)
         return set_err(ctx, MG_EINVAL, "symbolic lane range [%u,%u) outside batch of %u", first, first + n, ctx->L.n);
-    if (h->stack_cap > ctx->L.stack_cap || h->node_cap > ctx->S.node_cap || h->const_cap > ctx->S.const_cap ||
-        h->mem_cap > ctx->L.mem_cap || h->storage_cap > ctx->L.storage_cap)
-        return set_err(ctx, MG_EINVAL, "symbolic host image capacities exceed the allocation");
-    return MG_OK;
+    return check_sym_caps(ctx, h);
+}
+
+// the symbolic planes, each named once; the bounds are in units, as LaneBounds'
+static void plan_sym_scalars(XferPlan &x, const mg_sym_soa *h, const DevSym &S) {
+    x.scalar(h->n_nodes, S.n_nodes, 4);
+    x.scalar(h->n_consts, S.n_consts, 4);
+}
+
+struct SymBounds {
+    uint32_t stag, node, cval, mtag, sttag;
+};
+
+static void plan_sym_rows(XferPlan &x, const mg_sym_soa *h, const DevSym &S, const SymBounds &b) {
+    x.units(h->stag, h->stack_cap, 1, S.stag, b.stag);
+    x.units(h->node, h->node_cap, 4, S.node, b.node);
+    x.units(h->cval, h->const_cap, 8, S.cval, b.cval);
+    x.units(h->mtag, h->mem_cap, 1, S.mtag, b.mtag);
+    x.units(h->sttag, h->storage_cap, 2, S.sttag, b.sttag);
+}
+
+// mg_sym_upload and mg_sym_download: the arena only grows from each lane's node /
+// constant count and no step reads a row past it, so rows up to the range's largest
+// count cross PCIe, not the capacity; the tag planes go whole
+static SymBounds sym_range_bounds(const mg_sym_soa *h, uint32_t n) {
+    return SymBounds{XB_ALL, max_of(h->n_nodes, n), max_of(h->n_consts, n), XB_ALL, XB_ALL};
 }
 
 extern "C" int mg_sym_upload(mg_ctx *ctx, const mg_sym_soa *h, uint32_t first, uint32_t n) {
@@ -982,16 +1031,9 @@ extern "C" int mg_sym_upload(mg_ctx *ctx, const mg_sym_soa *h, uint32_t first, u
     for (uint32_t i = 0; i < n; ++i)
         if (h->n_nodes[i] > h->node_cap || h->n_consts[i] > h->const_cap)
             return set_err(ctx, MG_EINVAL, "lane %u: arena exceeds its host capacities", first + i);
-    // the arena only grows from each lane's node / constant count and no step reads a
-    // row past it: rows up to the range's largest count cross PCIe, not the capacity
     XferPlan x(n, first);
-    x.scalar(h->n_nodes, ctx->S.n_nodes, 4);
-    x.scalar(h->n_consts, ctx->S.n_consts, 4);
-    x.units(h->stag, h->stack_cap, 1, ctx->S.stag);
-    x.units(h->node, h->node_cap, 4, ctx->S.node, max_of(h->n_nodes, n));
-    x.units(h->cval, h->const_cap, 8, ctx->S.cval, max_of(h->n_consts, n));
-    x.units(h->mtag, h->mem_cap, 1, ctx->S.mtag);
-    x.units(h->sttag, h->storage_cap, 2, ctx->S.sttag);
+    plan_sym_scalars(x, h, ctx->S);
+    plan_sym_rows(x, h, ctx->S, sym_range_bounds(h, n));
     if ((rc = xfer_up(ctx, x))) return rc;
     HIPX(ctx, hipStreamSynchronize(ctx->stream));
     return MG_OK;
@@ -1004,15 +1046,10 @@ extern "C" int mg_sym_download(mg_ctx *ctx, mg_sym_soa *h, uint32_t first, uint3
     HIPX(ctx, hipSetDevice(ctx->device));
     // phase 1: the counts (they bound phase 2's arena rows)
     XferPlan x(n, first);
-    x.scalar(h->n_nodes, ctx->S.n_nodes, 4);
-    x.scalar(h->n_consts, ctx->S.n_consts, 4);
+    plan_sym_scalars(x, h, ctx->S);
     if ((rc = xfer_down(ctx, x))) return rc;
     XferPlan y(n, first);
-    y.units(h->stag, h->stack_cap, 1, ctx->S.stag);
-    y.units(h->node, h->node_cap, 4, ctx->S.node, max_of(h->n_nodes, n));
-    y.units(h->cval, h->const_cap, 8, ctx->S.cval, max_of(h->n_consts, n));
-    y.units(h->mtag, h->mem_cap, 1, ctx->S.mtag);
-    y.units(h->sttag, h->storage_cap, 2, ctx->S.sttag);
+    plan_sym_rows(y, h, ctx->S, sym_range_bounds(h, n));
     return xfer_down(ctx, y);
 }
 
@@ -1039,20 +1076,15 @@ extern "C" int mg_taint_alloc(mg_ctx *ctx, uint32_t obj_cap) {
     T.prog = ctx->d_tprog;
     T.force = ctx->d_tforce;
     const size_t N = ctx->L.N;
-    auto get = [&](void **p, size_t bytes) -> int {
-        if (hipMalloc(p, bytes) != hipSuccess) return set_err(ctx, MG_ENOMEM, "mg_taint_alloc: %zu bytes", bytes);
-        ctx->lane_allocs.push_back(*p);
-        return hipMemsetAsync(*p, 0, bytes, ctx->stream) == hipSuccess ? MG_OK : MG_EDEVICE;
-    };
-    if ((rc = get((void **)&T.sobj, (size_t)ctx->L.stack_cap * N * 4))) return rc;
-    if ((rc = get((void **)&T.omask, (size_t)obj_cap * N * 8))) return rc;
-    if ((rc = get((void **)&T.oremap, (size_t)obj_cap * N * 4))) return rc;
-    if ((rc = get((void **)&T.n_obj, N * 4))) return rc;
-    if ((rc = get((void **)&T.n_fixed, N * 4))) return rc;
-    if ((rc = get((void **)&T.n_atoms, N * 4))) return rc;
-    if ((rc = get((void **)&T.tflags, N * 4))) return rc;
-    if ((rc = get((void **)&T.sink, N * 8))) return rc;
-    if ((rc = get((void **)&T.ymask, N * 8))) return rc;
+    if ((rc = lane_alloc(ctx, T.sobj, (size_t)ctx->L.stack_cap * N, true))) return rc;
+    if ((rc = lane_alloc(ctx, T.omask, (size_t)obj_cap * N, true))) return rc;
+    if ((rc = lane_alloc(ctx, T.oremap, (size_t)obj_cap * N, true))) return rc;
+    if ((rc = lane_alloc(ctx, T.n_obj, N, true))) return rc;
+    if ((rc = lane_alloc(ctx, T.n_fixed, N, true))) return rc;
+    if ((rc = lane_alloc(ctx, T.n_atoms, N, true))) return rc;
+    if ((rc = lane_alloc(ctx, T.tflags, N, true))) return rc;
+    if ((rc = lane_alloc(ctx, T.sink, N, true))) return rc;
+    if ((rc = lane_alloc(ctx, T.ymask, N, true))) return rc;
     HIPX(ctx, hipStreamSynchronize(ctx->stream));
     ctx->T = T;
     return MG_OK;
@@ -1112,6 +1144,21 @@ static int check_taint_shape(mg_ctx *ctx, const mg_taint_soa *h, uint32_t first,
     return MG_OK;
 }
 
+// the taint planes, each named once; objects past the range's largest n_obj are unread
+static void plan_taint_scalars(XferPlan &x, const mg_taint_soa *h, const DevTaint &T) {
+    x.scalar(h->n_obj, T.n_obj, 4);
+    x.scalar(h->n_fixed, T.n_fixed, 4);
+    x.scalar(h->n_atoms, T.n_atoms, 4);
+    x.scalar(h->tflags, T.tflags, 4);
+    x.scalar(h->sink, T.sink, 8);
+    x.scalar(h->ymask, T.ymask, 8);
+}
+
+static void plan_taint_rows(XferPlan &x, const mg_taint_soa *h, const DevTaint &T, uint32_t n_obj) {
+    x.units(h->sobj, h->stack_cap, 1, T.sobj);
+    x.units(h->omask, h->obj_cap, 2, T.omask, n_obj);
+}
+
 extern "C" int mg_taint_upload(mg_ctx *ctx, const mg_taint_soa *h, uint32_t first, uint32_t n) {
     if (!ctx) return MG_EINVAL;
     int rc;
@@ -1128,16 +1175,9 @@ extern "C" int mg_taint_upload(mg_ctx *ctx, const mg_taint_soa *h, uint32_t firs
             if (so[k] >= h->obj_cap)
                 return set_err(ctx, MG_EINVAL, "lane %u slot %u: handle %u past obj_cap", first + i, k, so[k]);
     }
-    DevTaint &T = ctx->T;
     XferPlan x(n, first);
-    x.scalar(h->n_obj, T.n_obj, 4);
-    x.scalar(h->n_fixed, T.n_fixed, 4);
-    x.scalar(h->n_atoms, T.n_atoms, 4);
-    x.scalar(h->tflags, T.tflags, 4);
-    x.scalar(h->sink, T.sink, 8);
-    x.scalar(h->ymask, T.ymask, 8);
-    x.units(h->sobj, h->stack_cap, 1, T.sobj);
-    x.units(h->omask, h->obj_cap, 2, T.omask, max_of(h->n_obj, n));    // objects past n_obj are unread
+    plan_taint_scalars(x, h, ctx->T);
+    plan_taint_rows(x, h, ctx->T, max_of(h->n_obj, n));
     if ((rc = xfer_up(ctx, x))) return rc;
     HIPX(ctx, hipStreamSynchronize(ctx->stream));
     return MG_OK;
@@ -1148,18 +1188,11 @@ extern "C" int mg_taint_download(mg_ctx *ctx, mg_taint_soa *h, uint32_t first, u
     int rc;
     if ((rc = check_taint_shape(ctx, h, first, n))) return rc;
     HIPX(ctx, hipSetDevice(ctx->device));
-    DevTaint &T = ctx->T;
     XferPlan x(n, first);
-    x.scalar(h->n_obj, T.n_obj, 4);
-    x.scalar(h->n_fixed, T.n_fixed, 4);
-    x.scalar(h->n_atoms, T.n_atoms, 4);
-    x.scalar(h->tflags, T.tflags, 4);
-    x.scalar(h->sink, T.sink, 8);
-    x.scalar(h->ymask, T.ymask, 8);
+    plan_taint_scalars(x, h, ctx->T);
     if ((rc = xfer_down(ctx, x))) return rc;
     XferPlan y(n, first);
-    y.units(h->sobj, h->stack_cap, 1, T.sobj);
-    y.units(h->omask, h->obj_cap, 2, T.omask, max_of(h->n_obj, n));
+    plan_taint_rows(y, h, ctx->T, max_of(h->n_obj, n));
     return xfer_down(ctx, y);
 }
 
@@ -1181,55 +1214,32 @@ static int lanes_download(mg_ctx *ctx, mg_lane_soa *h, uint32_t first, uint32_t 
     HIPX(ctx, hipSetDevice(ctx->device));
     DevLanes &L = ctx->L;
     // live rows are bounded by the downloaded counts: a requested row field whose
-    // count array is skipped (NULL) has no bound
-    if (live) {
-        const struct { const void *rows; uint32_t cap; const void *count; const char *name; } need[] = {
-            {h->stack, h->stack_cap, h->sp, "sp"},
-            {h->storage, h->storage_cap, h->storage_count, "storage_count"},
-            {h->memory, h->mem_cap, h->msize, "msize"},
-            {h->trace, h->trace_cap, h->trace_len, "trace_len"},
-            {h->rec, h->rec_cap, h->rec_len, "rec_len"}};
-        for (const auto &f : need)
-            if (f.rows && f.cap && !f.count)
+    // count array is skipped (NULL) has no bound; a skipped (NULL) row field needs
+    // none, so its count array may be NULL too
+    LaneBounds b{XB_ALL, XB_ALL, XB_ALL, XB_ALL, XB_ALL, !live};
+    const struct { bool wanted; const uint32_t *count; const char *name; uint32_t *bound; } counted[] = {
+        {h->stack && h->stack_cap, h->sp, "sp", &b.stack},
+        {h->storage && h->storage_cap, h->storage_count, "storage_count", &b.storage},
+        {h->memory && h->mem_cap, h->msize, "msize", &b.mem_dwords},
+        {h->trace && h->trace_cap, h->trace_len, "trace_len", &b.trace},
+        {h->rec && h->rec_cap, h->rec_len, "rec_len", &b.rec}};
+    if (live)
+        for (const auto &f : counted)
+            if (f.wanted && !f.count)
                 return set_err(ctx, MG_EINVAL, "mg_lanes_download_live: %s is NULL but its rows are requested", f.name);
-    }
     // phase 1: the per-lane scalars (they bound phase 2's rows)
     XferPlan x(n, first);
-    x.scalar(h->code_id, L.code_id, 4);
-    x.scalar(h->pc, L.pc, 4);
-    x.scalar(h->sp, L.sp, 4);
-    x.scalar(h->msize, L.msize, 4);
-    x.scalar(h->depth, L.depth, 4);
-    x.scalar(h->status, L.status, 4);
-    x.scalar(h->aux, L.aux, 4);
-    x.scalar(h->steps, L.steps, 4);
-    x.scalar(h->flags, L.flags, 4);
-    x.scalar(h->calldata_len, L.calldata_len, 4);
-    x.scalar(h->storage_count, L.storage_count, 4);
-    x.scalar(h->ret_offset, L.ret_offset, 4);
-    x.scalar(h->ret_len, L.ret_len, 4);
-    x.scalar(h->gas_min, L.gas_min, 8);
-    x.scalar(h->gas_max, L.gas_max, 8);
-    x.scalar(h->gas_limit, L.gas_limit, 8);
-    if (h->trace_cap) x.scalar(h->trace_len, L.trace_len, 4);
-    if (h->rec_cap) x.scalar(h->rec_len, L.rec_len, 4);
-    if (h->fent) x.scalar(h->fent, L.fent, 4);
+    plan_lane_scalars(x, h, L, nullptr);
     if ((rc = xfer_down(ctx, x))) return rc;
     // phase 2: rows; live: only what a step can have written, below the
     // range's largest sp / storage count / msize / trace and record length
-    const uint32_t ALL = 0xffffffffu;
-    // a skipped (NULL) row field needs no bound, so its count array may be NULL too
-    auto bound = [&](const void *rows, const uint32_t *count) {
-        return live && rows ? max_of(count, n) : ALL;
-    };
+    if (live) {
+        for (const auto &f : counted)
+            if (f.wanted) *f.bound = max_of(f.count, n);
+        if (h->memory && h->mem_cap) b.mem_dwords = (b.mem_dwords + 3u) / 4u;   // msize counts bytes
+    }
     XferPlan y(n, first);
-    y.units(h->stack, h->stack_cap, 8, L.stack, bound(h->stack, h->sp));
-    if (!live) y.units(h->env, MG_ENV_WORDS, 8, L.env);
-    y.units(h->storage, h->storage_cap, 16, L.storage, bound(h->storage, h->storage_count));
-    y.bytes(h->memory, h->mem_cap, L.mem, live && h->memory ? (max_of(h->msize, n) + 3u) / 4u : ALL);
-    if (!live) y.bytes(h->calldata, h->calldata_cap, L.calldata);
-    if (h->trace_cap) y.units(h->trace, h->trace_cap, 1, L.trace, bound(h->trace, h->trace_len));
-    if (h->rec_cap) y.units(h->rec, h->rec_cap, 1, L.rec, bound(h->rec, h->rec_len));
+    plan_lane_rows(y, h, L, b, nullptr);
     return xfer_down(ctx, y);
 }
 
@@ -1239,17 +1249,12 @@ extern "C" int mg_set_loop_bound(mg_ctx *ctx, uint32_t bound) {
     return MG_OK;
 }
 
-static DevResetImage reset_image(const mg_ctx *ctx) {
-    return DevResetImage{ctx->i_pc, ctx->i_depth, ctx->i_status, ctx->i_aux, ctx->i_steps,
-                         ctx->i_storage_count, ctx->i_gas_min, ctx->i_gas_max, ctx->i_storage};
-}
-
 extern "C" int mg_lanes_reset(mg_ctx *ctx) {
     if (!ctx) return MG_EINVAL;
     if (!ctx->uploaded) return set_err(ctx, MG_ESTATE, "mg_lanes_reset before mg_lanes_upload");
     if (!ctx->init_fresh)
         return set_err(ctx, MG_ESTATE, "mg_lanes_reset needs an uploaded image with empty stacks and memory");
-    hipLaunchKernelGGL(k_reset, dim3(blocks_for(ctx->L.n)), dim3(256), 0, ctx->stream, ctx->L, reset_image(ctx));
+    hipLaunchKernelGGL(k_reset, dim3(blocks_for(ctx->L.n)), dim3(256), 0, ctx->stream, ctx->L, ctx->RI);
     HIPX(ctx, hipGetLastError());
     return MG_OK;
 }
@@ -1557,18 +1562,13 @@ extern "C" int mg_explore_alloc(mg_ctx *ctx, uint32_t path_cap) {
     DevExplore E{};
     E.path_cap = path_cap;
     const size_t N = ctx->L.N;
-    auto get = [&](void **p, size_t bytes) -> int {
-        if (hipMalloc(p, bytes) != hipSuccess) return set_err(ctx, MG_ENOMEM, "mg_explore_alloc: %zu bytes", bytes);
-        ctx->lane_allocs.push_back(*p);
-        return hipMemsetAsync(*p, 0, bytes, ctx->stream) == hipSuccess ? MG_OK : MG_EDEVICE;
-    };
     int rc;
     uint32_t *scratch = nullptr;        // path_len, root, isfree, free, kind, r1, r2, lcond, ljidx: [N] each
-    if ((rc = get((void **)&E.path, (size_t)path_cap * N * 4))) return rc;
-    if ((rc = get((void **)&scratch, (size_t)9u * N * 4))) return rc;
-    if ((rc = get((void **)&E.fork, (size_t)8u * N * 4))) return rc;
-    if ((rc = get((void **)&E.bt, (size_t)EX_MAX_BLOCKS * 6u * 4))) return rc;
-    if ((rc = get((void **)&ctx->d_ectr, sizeof(ExploreCtr)))) return rc;
+    if ((rc = lane_alloc(ctx, E.path, (size_t)path_cap * N, true))) return rc;
+    if ((rc = lane_alloc(ctx, scratch, (size_t)9u * N, true))) return rc;
+    if ((rc = lane_alloc(ctx, E.fork, (size_t)8u * N, true))) return rc;
+    if ((rc = lane_alloc(ctx, E.bt, (size_t)EX_MAX_BLOCKS * 6u, true))) return rc;
+    if ((rc = lane_alloc(ctx, ctx->d_ectr, 1, true))) return rc;
     E.path_len = scratch; E.root = scratch + N; E.isfree = scratch + 2u * N; E.free = scratch + 3u * N;
     E.kind = scratch + 4u * N; E.r1 = scratch + 5u * N; E.r2 = scratch + 6u * N;
     E.lcond = scratch + 7u * N; E.ljidx = scratch + 8u * N;
@@ -1811,16 +1811,15 @@ extern "C" int mg_harvest_download(mg_ctx *ctx, uint32_t *lanes, mg_lane_soa *h,
     const DevSym &S = ctx->S;
     const DevExplore &E = ctx->E;
     const uint32_t n = I.n;
+    int rc;
     if (!h || h->n != n)
         return set_err(ctx, MG_EINVAL, "mg_harvest_download: host image of %u lanes for a selection of %u", h ? h->n : 0, n);
-    if (h->stack_cap > L.stack_cap || h->mem_cap > L.mem_cap || h->mem_cap % 4 || h->calldata_cap > L.calldata_cap ||
-        h->calldata_cap % 4 || h->storage_cap > L.storage_cap || h->trace_cap > L.trace_cap || h->rec_cap > L.rec_cap)
-        return set_err(ctx, MG_EINVAL, "mg_harvest_download: host image capacities exceed the batch configuration");
+    if ((rc = check_host_caps(ctx, h))) return rc;
     if (sym) {
         if (!S.node) return set_err(ctx, MG_EINVAL, "mg_harvest_download: sym given without symbolic planes (mg_sym_alloc)");
-        if (sym->n != n || sym->stack_cap > L.stack_cap || sym->node_cap > S.node_cap || sym->const_cap > S.const_cap ||
-            sym->mem_cap > L.mem_cap || sym->storage_cap > L.storage_cap)
-            return set_err(ctx, MG_EINVAL, "mg_harvest_download: symbolic host image does not fit the selection or the allocation");
+        if (sym->n != n)
+            return set_err(ctx, MG_EINVAL, "mg_harvest_download: symbolic host image of %u lanes for a selection of %u", sym->n, n);
+        if ((rc = check_sym_caps(ctx, sym))) return rc;
     }
     if (path && !E.path) return set_err(ctx, MG_EINVAL, "mg_harvest_download: path given without explore planes (mg_explore_alloc)");
     if ((path != nullptr) != (path_len != nullptr) || (path != nullptr) != (root != nullptr))
@@ -1830,55 +1829,25 @@ extern "C" int mg_harvest_download(mg_ctx *ctx, uint32_t *lanes, mg_lane_soa *h,
     // every bound is the selection's largest count, clipped to the device capacity here and to
     // the host's by the plan: the gathers stay inside the planes whatever the image holds now
     const uint32_t b_sp = std::min(I.sp, L.stack_cap), b_ms = std::min(I.msize, L.mem_cap),
-                   b_st = std::min(I.storage_count, L.storage_cap), b_tr = std::min(I.trace_len, L.trace_cap),
-                   b_rec = std::min(I.rec_len, L.rec_cap);
+                   b_st = std::min(I.storage_count, L.storage_cap);
+    const LaneBounds b{b_sp, (b_ms + 3u) / 4u, b_st, std::min(I.trace_len, L.trace_cap), std::min(I.rec_len, L.rec_cap),
+                       true};
     XferPlan x(n, ctx->H.list);
-    // scalars first: k_xfer_pick takes their stage offsets as 32-bit words
+    // one phase, scalars first: k_xfer_pick takes their stage offsets as 32-bit words, and at
+    // most XP_MAX of them (19 of the lanes, 2 symbolic, 2 of the path; xfer_down refuses more)
     x.scalar(lanes, ctx->H.list, 4);     // the list itself: copied, not picked (xfer_down)
-    x.scalar(h->code_id, L.code_id, 4);
-    x.scalar(h->pc, L.pc, 4);
-    x.scalar(h->sp, L.sp, 4);
-    x.scalar(h->msize, L.msize, 4);
-    x.scalar(h->depth, L.depth, 4);
-    x.scalar(h->status, L.status, 4);
-    x.scalar(h->aux, L.aux, 4);
-    x.scalar(h->steps, L.steps, 4);
-    x.scalar(h->flags, L.flags, 4);
-    x.scalar(h->calldata_len, L.calldata_len, 4);
-    x.scalar(h->storage_count, L.storage_count, 4);
-    x.scalar(h->ret_offset, L.ret_offset, 4);
-    x.scalar(h->ret_len, L.ret_len, 4);
-    x.scalar(h->gas_min, L.gas_min, 8);
-    x.scalar(h->gas_max, L.gas_max, 8);
-    x.scalar(h->gas_limit, L.gas_limit, 8);
-    if (h->trace_cap) x.scalar(h->trace_len, L.trace_len, 4);
-    if (h->rec_cap) x.scalar(h->rec_len, L.rec_len, 4);
-    if (h->fent) x.scalar(h->fent, L.fent, 4);
-    if (sym) {
-        x.scalar(sym->n_nodes, S.n_nodes, 4);
-        x.scalar(sym->n_consts, S.n_consts, 4);
-    }
+    plan_lane_scalars(x, h, L, nullptr);
+    if (sym) plan_sym_scalars(x, sym, S);
     if (path) {
         x.scalar(path_len, E.path_len, 4);
         x.scalar(root, E.root, 4);
     }
-    x.units(h->stack, h->stack_cap, 8, L.stack, b_sp);
-    x.units(h->env, MG_ENV_WORDS, 8, L.env);
-    x.units(h->storage, h->storage_cap, 16, L.storage, b_st);
-    x.bytes(h->memory, h->mem_cap, L.mem, (b_ms + 3u) / 4u);
-    x.bytes(h->calldata, h->calldata_cap, L.calldata);
-    if (h->trace_cap) x.units(h->trace, h->trace_cap, 1, L.trace, b_tr);
-    if (h->rec_cap) x.units(h->rec, h->rec_cap, 1, L.rec, b_rec);
-    if (sym) {
-        x.units(sym->stag, sym->stack_cap, 1, S.stag, b_sp);
-        x.units(sym->node, sym->node_cap, 4, S.node, std::min(I.n_nodes, S.node_cap));
-        x.units(sym->cval, sym->const_cap, 8, S.cval, std::min(I.n_consts, S.const_cap));
-        x.units(sym->mtag, sym->mem_cap, 1, S.mtag, b_ms);
-        x.units(sym->sttag, sym->storage_cap, 2, S.sttag, b_st);
-    }
+    plan_lane_rows(x, h, L, b, nullptr);
+    if (sym)
+        plan_sym_rows(x, sym, S, SymBounds{b_sp, std::min(I.n_nodes, S.node_cap), std::min(I.n_consts, S.const_cap),
+                                           b_ms, b_st});
     const uint32_t b_path = path ? std::min(I.path_len, E.path_cap) : 0u;
     if (path) x.units(path, E.path_cap, 1, E.path, b_path);
-    int rc;
     if ((rc = xfer_down(ctx, x))) return rc;
     if (path) {
         // the plane above a lane's path_len holds what an earlier owner of the lane left
@@ -2097,7 +2066,6 @@ extern "C" int mg_run_batches(mg_ctx *ctx, const uint64_t hook_mask[4], uint32_t
     }
     // the stepping kernel re-initialises its lanes itself (reset_lane in its
     // prologue): one launch per batch
-    const DevResetImage R = reset_image(ctx);
     const LdsPlan plan = lds_plan(ctx);
     const int64_t kflags = (int64_t)k1_flags();
     // one event pair around the whole sequence, each batch reporting the mean:
@@ -2110,7 +2078,7 @@ extern "C" int mg_run_batches(mg_ctx *ctx, const uint64_t hook_mask[4], uint32_t
     for (uint32_t b = 0; b < n_batches; ++b) {
         if (per_batch_events || b == 0u) HIPX(ctx, hipEventRecord(ctx->ev_batch[2u * b], ctx->stream));
         int rc = launch_step(ctx, hook_mask, max_steps, max_depth, ctx->d_ctr_multi + (size_t)b * nb,
-                             nullptr, 0u, &R, &plan, kflags);
+                             nullptr, 0u, &ctx->RI, &plan, kflags);
         if (rc) return rc;
         if (per_batch_events || b + 1u == n_batches)
             HIPX(ctx, hipEventRecord(ctx->ev_batch[2u * b + 1u], ctx->stream));

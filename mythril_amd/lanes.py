@@ -105,6 +105,9 @@ _TAINT_FIELDS = ("sobj", "omask", "n_obj", "n_fixed", "n_atoms", "sink", "ymask"
 _U32_FIELDS = ("code_id", "pc", "sp", "msize", "depth", "status", "aux", "steps", "flags",
                "calldata_len", "storage_count", "ret_offset", "ret_len", "trace_len", "rec_len", "fent")
 _U64_FIELDS = ("gas_min", "gas_max", "gas_limit")
+# the per-lane rows, and every field of the lane image (mg_lane_soa); a new plane is added here
+_ROW_FIELDS = ("calldata", "env", "stack", "memory", "storage", "trace", "rec")
+_ALL_FIELDS = _U32_FIELDS + _U64_FIELDS + _ROW_FIELDS
 
 
 @dataclass
@@ -205,19 +208,10 @@ class LaneBatch:
 
     # ---- ctypes view ---------------------------------------------------
     def soa(self) -> MgLaneSoa:
-        s = MgLaneSoa()
-        s.n = self.shape.n
-        s.stack_cap, s.mem_cap = self.shape.stack_cap, self.shape.mem_cap
-        s.calldata_cap, s.storage_cap = self.shape.calldata_cap, self.shape.storage_cap
-        s.trace_cap = self.shape.trace_cap
-        s.rec_cap = self.shape.rec_cap
-        for f in _U32_FIELDS + _U64_FIELDS + ("calldata", "env", "stack", "memory", "storage",
-                                              "trace", "rec"):
-            arr = getattr(self, f)
-            assert arr.flags["C_CONTIGUOUS"]
-            setattr(s, f, arr.ctypes.data)
-        self._keep = s  # keep the struct alive with the arrays
-        return s
+        for f in _ALL_FIELDS:
+            assert getattr(self, f).flags["C_CONTIGUOUS"]
+        self._keep = self.soa_range(0, self.shape.n)  # keep the struct alive with the arrays
+        return self._keep
 
     def soa_range(self, first: int, n: int) -> MgLaneSoa:
         """Struct over lanes [first, first + n) of this image (for partial
@@ -230,8 +224,7 @@ class LaneBatch:
         s.calldata_cap, s.storage_cap = self.shape.calldata_cap, self.shape.storage_cap
         s.trace_cap = self.shape.trace_cap
         s.rec_cap = self.shape.rec_cap
-        for f in _U32_FIELDS + _U64_FIELDS + ("calldata", "env", "stack", "memory", "storage",
-                                              "trace", "rec"):
+        for f in _ALL_FIELDS:
             arr = getattr(self, f)
             setattr(s, f, arr.ctypes.data + first * arr.strides[0])
         self._keep_range = s
@@ -239,11 +232,13 @@ class LaneBatch:
 
     def copy(self) -> "LaneBatch":
         out = LaneBatch(self.shape)
-        for f in _U32_FIELDS + _U64_FIELDS + ("calldata", "env", "stack", "memory", "storage",
-                                              "trace", "rec") + (_SYM_FIELDS if self.symbolic else ()) + (
-                                                  _TAINT_FIELDS if self.taint else ()):
+        for f in self._fields():
             getattr(out, f)[...] = getattr(self, f)
         return out
+
+    def _fields(self) -> tuple:
+        """Every array of this image: the lane fields and the optional planes it has."""
+        return _ALL_FIELDS + (_SYM_FIELDS if self.symbolic else ()) + (_TAINT_FIELDS if self.taint else ())
 
     def regrown(self, shape: "LaneShape") -> "LaneBatch":
         """The same lanes in a batch of larger capacities (same n, calldata_cap,
@@ -254,9 +249,7 @@ class LaneBatch:
                 bool(shape.node_cap) != self.symbolic or bool(shape.obj_cap) != self.taint:
             raise ValueError("regrown: only capacities may change")
         out = LaneBatch(shape)
-        for f in _U32_FIELDS + _U64_FIELDS + ("calldata", "env", "stack", "memory", "storage", "trace",
-                                              "rec") + (_SYM_FIELDS if self.symbolic else ()) + (
-                                                  _TAINT_FIELDS if self.taint else ()):
+        for f in self._fields():
             src, dst = getattr(self, f), getattr(out, f)
             if src.ndim == 1:
                 dst[...] = src
@@ -429,10 +422,6 @@ def diff_batches(a: LaneBatch, b: LaneBatch, lanes: Optional[Iterable[int]] = No
             if (a.ret_offset[i], a.ret_len[i]) != (b.ret_offset[i], b.ret_len[i]):
                 out.append(f"lane {i}: return range differs")
     return out
-
-
-_ALL_FIELDS = _U32_FIELDS + _U64_FIELDS + ("calldata", "env", "stack", "memory", "storage",
-                                           "trace", "rec")
 
 
 def bucket_order(batch: LaneBatch) -> np.ndarray:

@@ -35,7 +35,7 @@ from test_gpu_explore import (INVALID, PATH_CAP, ROUNDS, SOURCES, _hand_image, _
 from test_gpu_fork import _full
 from test_harvest_model_cpu import (CHAIN, CHAIN_PATH_CAP, DEPTH, FINISHED, MAX_ITERATIONS, PATHS_PER_ROOT, ROOTS,
                                     SPARE_ONE_SHOT, SPARE_RECYCLE, chain_step, finished_paths)
-from xfermodel import DeviceImage, saturated, sentinel_filled, whole_diff
+from xfermodel import SCALARS, DeviceImage, saturated, sentinel_filled, whole_diff
 
 pytestmark = pytest.mark.gpu
 
@@ -249,6 +249,65 @@ def test_download_equals_the_model_word_for_word(dev, blocks, kind):
     assert lanes.tolist() == want_lanes.tolist() and whole_diff(slim, ref) == []
     assert (path is None) == (paths is None) and (paths is None or np.array_equal(path, ref_paths[0]))
     print(f"{kind}, MG_HARVEST_BLOCKS={blocks}: {checked} downloads equal the model word for word")
+
+
+def test_harvest_of_every_lane_equals_a_range_download(dev):
+    """The two users of the lane and symbolic transfer plans against each other: a
+    harvest of all 130 lanes (two 64-lane tiles and a tail of 2) and
+    download_range(first=0, n=130), both into sentinel-filled images of the full
+    capacities.  Below the selection's maxima -- so below each lane's own counts --
+    every cell is equal; above them the harvest image keeps its sentinels."""
+    _forget(dev)
+    n = 130
+    shape = dataclasses.replace(FULL, n=n)
+    if not hasattr(dev, "_harvest_cid"):
+        dev._harvest_cid = dev.load_code(test_gpu_fork.CODE)
+    rng = np.random.default_rng(0x130)
+    known, host = saturated(shape, rng, dev._harvest_cid), saturated(shape, rng, dev._harvest_cid)
+    # every count below its capacity: each plane has cells above the selection's maximum
+    rows = {"stack": "sp", "memory": "msize", "storage": "storage_count", "trace": "trace_len", "rec": "rec_len",
+            "stag": "sp", "node": "n_nodes", "cval": "n_consts", "mtag": "msize", "sttag": "storage_count"}
+    caps = {"sp": shape.stack_cap, "storage_count": shape.storage_cap, "trace_len": shape.trace_cap,
+            "rec_len": shape.rec_cap, "n_nodes": shape.node_cap, "n_consts": shape.const_cap}
+    for count, cap in caps.items():
+        getattr(host, count)[:] = rng.integers(0, cap, size=n)
+    host.msize[:] = 32 * rng.integers(0, shape.mem_cap // 32, size=n)
+    caps["msize"] = shape.mem_cap
+    paths = exploremodel.Paths(n, HPATH_CAP)
+    for l in range(n):
+        k = l % HPATH_CAP                                    # 0 .. path_cap - 1
+        paths.path_len[l] = k
+        paths.path[l, :k] = [(l * 131 + e * 7 + 1) & ALL for e in range(k)]
+        paths.root[l] = (l * 7) % n
+    dev.alloc(shape)
+    dev.explore_alloc(HPATH_CAP)
+    dev.explore_upload_paths(paths.path, paths.path_len, paths.root)
+    dev.upload(known)                                        # the whole device image is known and dirty
+    dev.upload(host)
+    info = dev.harvest_select(ALL)
+    assert (info.n, info.matched) == (n, n)
+    for count, cap in caps.items():
+        assert getattr(info, count) == int(getattr(host, count).max()) < cap, count
+    got, ref = sentinel_filled(shape), sentinel_filled(shape)
+    rc, lanes, path, path_len, root = _download(dev, got, True, HPATH_CAP)
+    assert rc == MG_OK, dev.lib.mg_last_error(dev.ctx)
+    dev.download_range(ref, 0, n)
+    assert lanes.tolist() == list(range(n))
+    for f in list(SCALARS) + ["fent", "trace_len", "rec_len", "n_nodes", "n_consts", "env", "calldata"]:
+        assert np.array_equal(getattr(got, f), getattr(ref, f)), f
+    for f, count in rows.items():
+        top = getattr(info, count)
+        g, r = getattr(got, f), getattr(ref, f)
+        assert np.array_equal(g[:, :top], r[:, :top]), f
+        for i in range(n):                                   # what is live is what was uploaded
+            k = int(getattr(host, count)[i])
+            assert np.array_equal(g[i, :k], getattr(host, f)[i, :k]), (f, i)
+        above = np.ascontiguousarray(g[:, top:]).view(np.uint8)
+        assert above.size and (above == 0xA5).all(), f
+    want = dev.explore_paths(0, n)
+    for a, b in zip((path, path_len, root), want):
+        assert np.array_equal(a, b)
+    assert np.array_equal(path_len, paths.path_len) and np.array_equal(root, paths.root)
 
 
 # ------------------------------------------------------------------------ c. refusals

@@ -5,7 +5,7 @@ the CPU end-to-end tests run with the transfers the GPU has.
 """
 import numpy as np
 
-from mythril_amd.lanes import MG_FENT_NONE, MG_HALT_STOP, LaneBatch, LaneShape
+from mythril_amd.lanes import _ALL_FIELDS, MG_FENT_NONE, MG_HALT_STOP, LaneBatch, LaneShape
 from oracle_device import OracleDevice
 from xfermodel import (DeviceImage, fields_of, live_diff, live_equal, saturated, sentinel_filled, whole_diff)
 
@@ -226,3 +226,27 @@ def test_oracle_device_honours_live_and_bounded_uploads():
     model.download(want, 9, 6, host_first=0)
     assert whole_diff(slim, want) == []
     assert np.array_equal(slim.stack, model.img.stack[9:15, :SLIM.stack_cap])
+
+
+def test_soa_is_soa_range_of_every_lane():
+    """soa() is soa_range(0, n), and soa_range(first, n) points first rows into each array."""
+    shape = LaneShape(n=12, stack_cap=5, mem_cap=64, calldata_cap=8, storage_cap=3, trace_cap=6, rec_cap=7,
+                      node_cap=4, const_cap=2, obj_cap=20)
+    b = LaneBatch(shape)
+    whole, ranged = b.soa(), b.soa_range(0, shape.n)
+    names = [f for f, _ in type(whole)._fields_ if not f.startswith("_pad")]
+    assert {"n", "stack_cap", "mem_cap", "calldata_cap", "storage_cap", "trace_cap", "rec_cap"} < set(names)
+    arrays = [f for f in names if not (f == "n" or f.endswith("_cap"))]
+    assert len(arrays) == 26 and set(arrays) == set(_ALL_FIELDS)
+    for f in names:
+        assert getattr(whole, f) == getattr(ranged, f), f
+    for f in arrays:
+        assert getattr(whole, f) == getattr(b, f).ctypes.data, f
+    for f in names:
+        if f.endswith("_cap"):
+            assert getattr(whole, f) == getattr(shape, f), f
+    part = b.soa_range(7, 5)
+    assert part.n == 5 and part.trace_cap == 6 and part.rec_cap == 7
+    for f in arrays:
+        arr = getattr(b, f)
+        assert getattr(part, f) == arr.ctypes.data + 7 * arr.strides[0], f
