@@ -692,7 +692,9 @@ int         mg_explore_resume(mg_ctx *ctx, const uint64_t hook_mask[4], uint32_t
  * reads one small block back under one stream synchronisation, and its numbers of
  * launches and copies depend on none of n_lanes, matched and n; it writes nothing
  * of the lane image.  MG_HARVEST_BLOCKS (1..1024, default 1024, read per call) caps
- * the number of blocks that scan the statuses.
+ * the number of blocks that scan the statuses; MG_EXPLORE_BLOCKS (the same range,
+ * default and reading) caps those of mg_explore's and mg_explore_resume's plan.
+ * Neither changes a result.
  * Checked on the host before any launch: MG_ESTATE without a batch or an upload;
  * MG_EINVAL for a NULL info, a NULL skip with n_skip > 0, or a skip that is not
  * strictly ascending with every entry below n_lanes (the message names the index).

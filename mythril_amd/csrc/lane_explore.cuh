@@ -7,15 +7,12 @@
 // k_explore_path.  The plan fills the arrays of a ForkArgs in device memory; the
 // host passes only counts by value.
 //
-//   k_explore_scan   one thread per lane.  fork_probe (lane_fork.cuh) classifies the
-//                    lane; the forkable lanes are ranked in ascending lane order,
-//                    separately for EX_INPLACE (invalid target: fall-through only)
-//                    and EX_JUMP (needs a free lane): a __ballot / popcount rank
-//                    inside each wave64, the four wave totals of a block through
-//                    LDS, a running carry over the block's tiles.  Block b owns the
-//                    lanes [b * chunk, (b + 1) * chunk), chunk a multiple of 256, so
-//                    there are at most EX_MAX_BLOCKS block totals whatever n is.
-//   k_explore_totals one block.  Exclusive scan of the block totals; the counters.
+// The plan is lane_rank.cuh's ranked selection (the block geometry, the order and the
+// free list's invariant are stated there), after k_lane_mark on isfree:
+//   k_explore_scan   fork_probe (lane_fork.cuh) classifies the lane.  Ranked: EX_INPLACE
+//                    (invalid target: fall-through only) and EX_JUMP (needs a free
+//                    lane); only counted: the running and the path-full lanes.
+//   k_explore_totals one block.  Offsets of the two ranked classes; the counters.
 //   k_explore_emit   one thread per lane.  With K1 / K2 the lane's global ranks among
 //                    the EX_INPLACE / EX_JUMP lanes and `avail` free lanes unused,
 //                    an EX_JUMP lane forks when K2 < avail (the lowest lanes win) and
@@ -23,8 +20,6 @@
 //                    free[base + K2] and its copy is copy number K2.  Sources and the
 //                    free list both ascend, so the copy list ascends by destination,
 //                    which k_fork_copy's mapping relies on.
-//
-// No block waits for another: the three kernels are ordered by the stream.
 //
 // Read-before-write: the fall-through is in place (dst_fall == src), so the jump
 // child is copied from a lane the fall-through update rewrites.  Nothing before
@@ -39,7 +34,6 @@
 // above every row it read, and no other thread touches that fork's lanes.
 #pragma once
 
-#define EX_MAX_BLOCKS 1024u
 #define EX_NONE 0u      // not a source
 #define EX_INPLACE 1u   // forkable, the target is no JUMPDEST: fall-through only, no free lane
 #define EX_JUMP 2u      // forkable with a valid target: needs one free lane
@@ -54,8 +48,8 @@ struct DevExplore {
     uint32_t *isfree;     // 1: the lane is in the unused part of the free list
     uint32_t *free;       // the call's free list
     uint32_t *kind, *r1, *r2, *lcond, *ljidx;   // per lane: class, block-local ranks, probe results
-    uint32_t *bt;         // [EX_MAX_BLOCKS][4] block totals: in place, jump, running, path full
-    uint32_t *boff;       // [EX_MAX_BLOCKS][2] exclusive block offsets: in place, jump
+    uint32_t *bt;         // [RK_MAX_BLOCKS][4] block totals: in place, jump, running, path full
+    uint32_t *boff;       // [RK_MAX_BLOCKS][2] exclusive block offsets: in place, jump
     uint32_t *fork;       // [8][N] the ForkArgs arrays: src, dst_fall, dst_jump, copy_fork, copy_dst, made, cond, jidx
 };
 
@@ -70,21 +64,11 @@ __global__ __launch_bounds__(256) void k_explore_init(DevExplore E, uint32_t n) 
     E.root[l] = l; E.path_len[l] = 0u; E.isfree[l] = 0u;
 }
 
-__global__ __launch_bounds__(256) void k_explore_mark(DevExplore E, uint32_t n_free) {
-    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j < n_free) E.isfree[E.free[j]] = 1u;   // the host checked every entry against n_lanes
-}
-
 __global__ __launch_bounds__(256) void k_explore_scan(DevLanes L, DevSym S, DevExplore E,
-                                                      const DevCode *__restrict__ codes,
-                                                      const uint8_t *__restrict__ a8,
-                                                      const uint32_t *__restrict__ a32, uint32_t n_codes,
-                                                      uint32_t chunk) {
-    __shared__ uint32_t sh[4][4];
-    const uint32_t x = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    const unsigned long long below = (1ull << x) - 1ull;
+                                                      const DevCode *__restrict__ codes, const uint8_t *__restrict__ a8,
+                                                      const uint32_t *__restrict__ a32, uint32_t n_codes, uint32_t chunk) {
     const uint32_t lo = blockIdx.x * chunk;
-    uint32_t c1 = 0u, c2 = 0u, c_run = 0u, c_full = 0u;      // the block's carry over its tiles
+    uint32_t c[4] = {0u, 0u, 0u, 0u};                        // the block's carries over its tiles
     for (uint32_t t = 0; t < chunk; t += 256u) {
         const uint32_t l = lo + t + threadIdx.x;
         uint32_t kind = EX_NONE, cond = 0u, jidx = MG_JRES_NONE;
@@ -94,63 +78,42 @@ __global__ __launch_bounds__(256) void k_explore_scan(DevLanes L, DevSym S, DevE
             if (!E.isfree[l] && fork_probe(L, S, codes, a8, a32, n_codes, l, true, cond, jidx))
                 kind = E.path_len[l] >= E.path_cap ? EX_FULL : jidx != MG_JRES_NONE ? EX_JUMP : EX_INPLACE;
         }
-        const unsigned long long b1 = __ballot(kind == EX_INPLACE), b2 = __ballot(kind == EX_JUMP);
-        const unsigned long long br = __ballot(running), bf = __ballot(kind == EX_FULL);
-        if (x == 0u) {
-            sh[w][0] = (uint32_t)__popcll(b1); sh[w][1] = (uint32_t)__popcll(b2);
-            sh[w][2] = (uint32_t)__popcll(br); sh[w][3] = (uint32_t)__popcll(bf);
-        }
-        __syncthreads();
-        uint32_t p1 = 0u, p2 = 0u, t1 = 0u, t2 = 0u, tr = 0u, tf = 0u;
-#pragma unroll
-        for (uint32_t k = 0; k < 4u; ++k) {
-            if (k < w) { p1 += sh[k][0]; p2 += sh[k][1]; }
-            t1 += sh[k][0]; t2 += sh[k][1]; tr += sh[k][2]; tf += sh[k][3];
-        }
+        const bool flag[4] = {kind == EX_INPLACE, kind == EX_JUMP, running, kind == EX_FULL};
+        uint32_t r[4], tot[4];                               // r[2] and r[3] are not read
+        rank_tile<4>(flag, r, tot);
         if (l < L.n) {
             E.kind[l] = kind;
-            E.r1[l] = c1 + p1 + (uint32_t)__popcll(b1 & below);
-            E.r2[l] = c2 + p2 + (uint32_t)__popcll(b2 & below);
+            E.r1[l] = c[0] + r[0]; E.r2[l] = c[1] + r[1];
             E.lcond[l] = cond; E.ljidx[l] = jidx;
         }
-        c1 += t1; c2 += t2; c_run += tr; c_full += tf;
-        __syncthreads();                                     // sh is rewritten by the next tile
+        c[0] += tot[0]; c[1] += tot[1]; c[2] += tot[2]; c[3] += tot[3];
     }
     if (threadIdx.x == 0u) {
-        uint32_t *o = E.bt + 4u * blockIdx.x;
-        o[0] = c1; o[1] = c2; o[2] = c_run; o[3] = c_full;
+        uint32_t *o = E.bt + 4u * blockIdx.x;                // in place, jump, running, path full
+        o[0] = c[0]; o[1] = c[1]; o[2] = c[2]; o[3] = c[3];
     }
 }
 
-// one block of EX_MAX_BLOCKS threads: nb <= EX_MAX_BLOCKS block totals
+// one block of RK_MAX_BLOCKS threads: nb <= RK_MAX_BLOCKS block totals
 __global__ __launch_bounds__(1024) void k_explore_totals(DevExplore E, uint32_t nb, uint32_t avail,
                                                          const DevCounters *__restrict__ step_ctr, uint32_t n_step_ctr,
                                                          ExploreCtr *__restrict__ out) {
-    __shared__ uint32_t s1[2][EX_MAX_BLOCKS], s2[2][EX_MAX_BLOCKS];
     __shared__ uint32_t s_run, s_full;
     __shared__ unsigned long long s_steps;
     const uint32_t t = threadIdx.x;
     if (t == 0u) { s_run = 0u; s_full = 0u; s_steps = 0ull; }
-    const uint32_t v1 = t < nb ? E.bt[4u * t] : 0u, v2 = t < nb ? E.bt[4u * t + 1u] : 0u;
-    s1[0][t] = v1; s2[0][t] = v2;
+    const uint32_t v[2] = {t < nb ? E.bt[4u * t] : 0u, t < nb ? E.bt[4u * t + 1u] : 0u};
     __syncthreads();
     if (t < nb) { atomicAdd(&s_run, E.bt[4u * t + 2u]); atomicAdd(&s_full, E.bt[4u * t + 3u]); }
     unsigned long long steps = 0ull;
-    for (uint32_t k = t; k < n_step_ctr; k += EX_MAX_BLOCKS) steps += step_ctr[k].lane_steps;
+    for (uint32_t i = t; i < n_step_ctr; i += RK_MAX_BLOCKS) steps += step_ctr[i].lane_steps;
     if (steps) atomicAdd(&s_steps, steps);
-    uint32_t cur = 0u;
-    for (uint32_t d = 1u; d < EX_MAX_BLOCKS; d <<= 1) {      // inclusive scan, double-buffered
-        const uint32_t a = s1[cur][t] + (t >= d ? s1[cur][t - d] : 0u);
-        const uint32_t b = s2[cur][t] + (t >= d ? s2[cur][t - d] : 0u);
-        s1[cur ^ 1u][t] = a; s2[cur ^ 1u][t] = b;
-        cur ^= 1u;
-        __syncthreads();
-    }
-    if (t < nb) { E.boff[2u * t] = s1[cur][t] - v1; E.boff[2u * t + 1u] = s2[cur][t] - v2; }
+    uint32_t off[2], k[2];
+    rank_block_offsets<2>(v, off, k);                        // its barriers order the three sums too
+    if (t < nb) { E.boff[2u * t] = off[0]; E.boff[2u * t + 1u] = off[1]; }
     if (t == 0u) {
-        const uint32_t k1 = s1[cur][EX_MAX_BLOCKS - 1u], k2 = s2[cur][EX_MAX_BLOCKS - 1u];
-        const uint32_t copies = min(k2, avail);
-        out->forks = k1 + copies; out->copies = copies; out->running = s_run; out->starved = k2 - copies;
+        const uint32_t copies = min(k[1], avail);
+        out->forks = k[0] + copies; out->copies = copies; out->running = s_run; out->starved = k[1] - copies;
         out->path_full = s_full; out->_pad = 0u; out->lane_steps = s_steps;
     }
 }

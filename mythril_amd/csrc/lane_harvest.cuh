@@ -2,26 +2,18 @@
 // a batch chosen where the statuses are, and their rows gathered through a lane
 // list (include/mythgpu.h states the contract).
 //
-// The selection is lane_explore.cuh's plan pattern restated for one class (that
-// file's kernels are left as they are; nothing is shared with them):
-//
-//   k_harvest_mark    one thread per skip entry: skipm[skip[j]] = 1 (skipm was cleared).
-//   k_harvest_scan    block b owns the lanes [b * chunk, (b + 1) * chunk), chunk a
-//                     multiple of 256, so there are at most HV_MAX_BLOCKS block totals
-//                     whatever n is.  A lane matches when its status is below 32, that
-//                     bit of the mask is set and it is not marked.  The matching lanes
-//                     are ranked in ascending lane order: a __ballot / popcount rank
-//                     inside each wave64, the four wave totals of a block through LDS,
-//                     a running carry over the block's tiles.
-//   k_harvest_totals  one block.  Exclusive scan of the block totals; n and matched;
-//                     the eight maxima zeroed for the emit kernel.
+// The selection is lane_rank.cuh's ranked selection for one class (the block geometry,
+// the order and the skip list's invariant are stated there), after k_lane_mark on skipm:
+//   k_harvest_scan    a lane matches when its status is below 32, that bit of the mask
+//                     is set and it is not marked.
+//   k_harvest_totals  one block.  The block offsets; n and matched; the eight maxima
+//                     zeroed for the emit kernel.
 //   k_harvest_emit    one thread per lane.  A matching lane of global rank r < max_lanes
 //                     is selected: list[r] = lane.  The maxima of the eight counts are
 //                     taken over the selected lanes only: a wave reduction, then at most
 //                     one atomicMax per wave and field.
 //
-// No block waits for another: the kernels are ordered by the stream.  None of them
-// writes the lane image.
+// None of the kernels writes the lane image.
 //
 // The gather kernels are mythgpu.hip's k_xfer_gather with the device lane taken
 // from the list.  Invariant they rely on: every entry list[0 .. n) was written by
@@ -31,7 +23,6 @@
 // mg_explore_alloc drop the selection).
 #pragma once
 
-#define HV_MAX_BLOCKS 1024u
 #define HV_NONE 0xffffffffu     // rank of a lane that does not match
 #define HV_FIELDS 8u            // sp, msize, storage_count, trace_len, rec_len, n_nodes, n_consts, path_len
 
@@ -40,8 +31,8 @@ struct DevHarvest {
     uint32_t *skip;     // [N] the call's skip list
     uint32_t *rank;     // [N] block-local rank among the matching lanes, or HV_NONE
     uint32_t *list;     // [N] the selection, ascending
-    uint32_t *bt;       // [HV_MAX_BLOCKS] block totals
-    uint32_t *boff;     // [HV_MAX_BLOCKS] exclusive block offsets
+    uint32_t *bt;       // [RK_MAX_BLOCKS] block totals
+    uint32_t *boff;     // [RK_MAX_BLOCKS] exclusive block offsets
     uint32_t *info;     // [2 + HV_FIELDS] n, matched, the maxima (mg_harvest_info's first words)
 };
 
@@ -50,59 +41,33 @@ struct HarvestCounts {
     const uint32_t *f[HV_FIELDS];
 };
 
-__global__ __launch_bounds__(256) void k_harvest_mark(DevHarvest H, uint32_t n_skip) {
-    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j < n_skip) H.skipm[H.skip[j]] = 1u;     // the host checked every entry against n_lanes
-}
-
 __global__ __launch_bounds__(256) void k_harvest_scan(DevHarvest H, const uint32_t *__restrict__ status, uint32_t n,
                                                       uint32_t mask, uint32_t chunk) {
-    __shared__ uint32_t sh[4];
-    const uint32_t x = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    const unsigned long long below = (1ull << x) - 1ull;
     const uint32_t lo = blockIdx.x * chunk;
     uint32_t carry = 0u;                                     // the block's carry over its tiles
     for (uint32_t t = 0; t < chunk; t += 256u) {
         const uint32_t l = lo + t + threadIdx.x;
-        bool match = false;
+        bool match[1] = {false};
         if (l < n) {
             const uint32_t st = status[l];
-            match = st < 32u && (mask >> st & 1u) && !H.skipm[l];
+            match[0] = st < 32u && (mask >> st & 1u) && !H.skipm[l];
         }
-        const unsigned long long b = __ballot(match);
-        if (x == 0u) sh[w] = (uint32_t)__popcll(b);
-        __syncthreads();
-        uint32_t p = 0u, tot = 0u;
-#pragma unroll
-        for (uint32_t k = 0; k < 4u; ++k) {
-            if (k < w) p += sh[k];
-            tot += sh[k];
-        }
-        if (l < n) H.rank[l] = match ? carry + p + (uint32_t)__popcll(b & below) : HV_NONE;
-        carry += tot;
-        __syncthreads();                                     // sh is rewritten by the next tile
+        uint32_t r[1], tot[1];
+        rank_tile<1>(match, r, tot);
+        if (l < n) H.rank[l] = match[0] ? carry + r[0] : HV_NONE;
+        carry += tot[0];
     }
     if (threadIdx.x == 0u) H.bt[blockIdx.x] = carry;
 }
 
-// one block of HV_MAX_BLOCKS threads: nb <= HV_MAX_BLOCKS block totals
+// one block of RK_MAX_BLOCKS threads: nb <= RK_MAX_BLOCKS block totals
 __global__ __launch_bounds__(1024) void k_harvest_totals(DevHarvest H, uint32_t nb, uint32_t max_lanes) {
-    __shared__ uint32_t s[2][HV_MAX_BLOCKS];
     const uint32_t t = threadIdx.x;
-    const uint32_t v = t < nb ? H.bt[t] : 0u;
-    s[0][t] = v;
-    __syncthreads();
-    uint32_t cur = 0u;
-    for (uint32_t d = 1u; d < HV_MAX_BLOCKS; d <<= 1) {      // inclusive scan, double-buffered
-        s[cur ^ 1u][t] = s[cur][t] + (t >= d ? s[cur][t - d] : 0u);
-        cur ^= 1u;
-        __syncthreads();
-    }
-    if (t < nb) H.boff[t] = s[cur][t] - v;
-    if (t == 0u) {
-        const uint32_t matched = s[cur][HV_MAX_BLOCKS - 1u];
-        H.info[0] = min(matched, max_lanes); H.info[1] = matched;
-    }
+    const uint32_t v[1] = {t < nb ? H.bt[t] : 0u};
+    uint32_t off[1], matched[1];
+    rank_block_offsets<1>(v, off, matched);
+    if (t < nb) H.boff[t] = off[0];
+    if (t == 0u) { H.info[0] = min(matched[0], max_lanes); H.info[1] = matched[0]; }
     if (t < HV_FIELDS) H.info[2u + t] = 0u;
 }
 

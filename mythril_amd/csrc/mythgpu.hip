@@ -21,6 +21,7 @@
 #include "lane_step.cuh"
 #include "sym_step.cuh"
 #include "lane_fork.cuh"
+#include "lane_rank.cuh"
 #include "lane_explore.cuh"
 #include "lane_harvest.cuh"
 #include "path_eval.cuh"
@@ -1547,6 +1548,53 @@ extern "C" int mg_step_until(mg_ctx *ctx, const uint64_t hook_mask[4], uint32_t 
     return MG_OK;
 }
 
+// ---- ranked selection, host side (lane_rank.cuh): mg_explore and mg_harvest_select ----
+// a lane list of an entry point `who`: given, inside the batch, strictly ascending
+static int check_lane_list(mg_ctx *ctx, const char *who, const char *name, const uint32_t *list, uint32_t n_list,
+                           uint32_t n_lanes) {
+    if (n_list && !list) return set_err(ctx, MG_EINVAL, "%s: %s is null with %u entries", who, name, n_list);
+    for (uint32_t j = 0; j < n_list; ++j) {
+        if (list[j] >= n_lanes)
+            return set_err(ctx, MG_EINVAL, "%s: %s[%u] = %u outside batch of %u", who, name, j, list[j], n_lanes);
+        if (j && list[j] <= list[j - 1u])
+            return set_err(ctx, MG_EINVAL, "%s: %s[%u] = %u is not above %s[%u] = %u", who, name, j, list[j], name,
+                           j - 1u, list[j - 1u]);
+    }
+    return MG_OK;
+}
+
+// block b of a scan owns lanes [b * chunk, (b + 1) * chunk): nb <= max_blocks block totals
+struct RankGeometry {
+    uint32_t tiles, chunk, nb;
+};
+static RankGeometry rank_geometry(uint32_t n, uint32_t max_blocks) {
+    const uint32_t tiles = blocks_for(n), chunk = ((tiles + max_blocks - 1u) / max_blocks) * 256u;
+    return RankGeometry{tiles, chunk, (n + chunk - 1u) / chunk};
+}
+
+// MG_EXPLORE_BLOCKS / MG_HARVEST_BLOCKS, read per call, cap the scan blocks: a small
+// batch can then cross both the carry over a block's tiles and the block offsets
+static uint32_t rank_max_blocks(const char *env) {
+    const char *e = getenv(env);
+    const long v = e ? strtol(e, nullptr, 10) : 0;
+    return v >= 1 && v <= (long)RK_MAX_BLOCKS ? (uint32_t)v : RK_MAX_BLOCKS;
+}
+
+// the path planes, named once; `bound` is in entries, as LaneBounds'
+static void plan_paths(XferPlan &x, uint32_t *path, uint32_t *path_len, uint32_t *root, const DevExplore &E,
+                       uint32_t bound) {
+    x.scalar(path_len, E.path_len, 4);
+    x.scalar(root, E.root, 4);
+    x.units(path, E.path_cap, 1, E.path, bound);
+}
+
+// host rows [n][cap]: 0 at and above each lane's path_len (a download leaves the rows from
+// `bound` up as they were, and the plane above path_len holds what an earlier owner left)
+static void zero_path_tails(uint32_t *path, const uint32_t *path_len, uint32_t n, size_t cap, uint32_t bound) {
+    for (uint32_t i = 0; i < n; ++i)
+        for (size_t e = std::min(path_len[i], bound); e < cap; ++e) path[(size_t)i * cap + e] = 0u;
+}
+
 // ---- mg_explore (lane_explore.cuh) --------------------------------------------
 extern "C" int mg_explore_alloc(mg_ctx *ctx, uint32_t path_cap) {
     if (!ctx) return MG_EINVAL;
@@ -1567,12 +1615,12 @@ extern "C" int mg_explore_alloc(mg_ctx *ctx, uint32_t path_cap) {
     if ((rc = lane_alloc(ctx, E.path, (size_t)path_cap * N, true))) return rc;
     if ((rc = lane_alloc(ctx, scratch, (size_t)9u * N, true))) return rc;
     if ((rc = lane_alloc(ctx, E.fork, (size_t)8u * N, true))) return rc;
-    if ((rc = lane_alloc(ctx, E.bt, (size_t)EX_MAX_BLOCKS * 6u, true))) return rc;
+    if ((rc = lane_alloc(ctx, E.bt, (size_t)RK_MAX_BLOCKS * 6u, true))) return rc;
     if ((rc = lane_alloc(ctx, ctx->d_ectr, 1, true))) return rc;
     E.path_len = scratch; E.root = scratch + N; E.isfree = scratch + 2u * N; E.free = scratch + 3u * N;
     E.kind = scratch + 4u * N; E.r1 = scratch + 5u * N; E.r2 = scratch + 6u * N;
     E.lcond = scratch + 7u * N; E.ljidx = scratch + 8u * N;
-    E.boff = E.bt + 4u * EX_MAX_BLOCKS;
+    E.boff = E.bt + 4u * RK_MAX_BLOCKS;
     HIPX(ctx, hipStreamSynchronize(ctx->stream));
     ctx->E = E;
     ctx->hv_valid = false;
@@ -1593,17 +1641,10 @@ static int explore_run(mg_ctx *ctx, const uint64_t hook_mask[4], uint32_t max_st
     if (!ctx->E.path) return set_err(ctx, MG_ESTATE, "mg_explore needs explore planes (mg_explore_alloc)");
     if (max_rounds == 0u) return set_err(ctx, MG_EINVAL, "mg_explore: max_rounds is 0 (the loop is bounded by it)");
     const uint32_t n = ctx->L.n, N = ctx->L.N;
-    if (n_free && !free_lanes) return set_err(ctx, MG_EINVAL, "mg_explore: free_lanes is null with n_free = %u", n_free);
-    for (uint32_t j = 0; j < n_free; ++j) {
-        if (free_lanes[j] >= n)
-            return set_err(ctx, MG_EINVAL, "mg_explore: free_lanes[%u] = %u outside batch of %u", j, free_lanes[j], n);
-        if (j && free_lanes[j] <= free_lanes[j - 1u])
-            return set_err(ctx, MG_EINVAL, "mg_explore: free_lanes[%u] = %u is not above free_lanes[%u] = %u", j,
-                           free_lanes[j], j - 1u, free_lanes[j - 1u]);
-    }
+    int rc;
+    if ((rc = check_lane_list(ctx, "mg_explore", "free_lanes", free_lanes, n_free, n))) return rc;
     HIPX(ctx, hipSetDevice(ctx->device));
     const DevExplore &E = ctx->E;
-    int rc;
     if (n_free) {
         if ((rc = ensure_hxfer(ctx, (size_t)n_free * 4u))) return rc;
         std::memcpy(ctx->h_xfer, free_lanes, (size_t)n_free * 4u);
@@ -1612,12 +1653,10 @@ static int explore_run(mg_ctx *ctx, const uint64_t hook_mask[4], uint32_t max_st
     HIPX(ctx, hipEventRecord(ctx->ev0, ctx->stream));
     if (resume) HIPX(ctx, hipMemsetAsync(E.isfree, 0, (size_t)n * 4u, ctx->stream));
     else hipLaunchKernelGGL(k_explore_init, dim3(blocks_for(n)), dim3(256), 0, ctx->stream, E, n);
-    if (n_free) hipLaunchKernelGGL(k_explore_mark, dim3(blocks_for(n_free)), dim3(256), 0, ctx->stream, E, n_free);
+    if (n_free)
+        hipLaunchKernelGGL(k_lane_mark, dim3(blocks_for(n_free)), dim3(256), 0, ctx->stream, E.isfree, E.free, n_free);
     HIPX(ctx, hipGetLastError());
-    // block b of the plan owns lanes [b * chunk, (b + 1) * chunk): at most EX_MAX_BLOCKS totals
-    const uint32_t tiles = blocks_for(n);
-    const uint32_t chunk = ((tiles + EX_MAX_BLOCKS - 1u) / EX_MAX_BLOCKS) * 256u;
-    const uint32_t nb = (n + chunk - 1u) / chunk;
+    const RankGeometry g = rank_geometry(n, rank_max_blocks("MG_EXPLORE_BLOCKS"));
     const uint32_t n_step_ctr = blocks_for(n, lane_block(ctx));
     ForkArgs F{};
     F.n_codes = (uint32_t)ctx->codes.size(); F.cov_on = ctx->cfg.coverage ? 1u : 0u;
@@ -1629,11 +1668,11 @@ static int explore_run(mg_ctx *ctx, const uint64_t hook_mask[4], uint32_t max_st
     for (uint32_t round = 0; round < max_rounds; ++round) {
         if ((rc = launch_step(ctx, hook_mask, max_steps, max_depth, ctx->d_ctr))) return rc;
         const uint32_t avail = n_free - used;
-        hipLaunchKernelGGL(k_explore_scan, dim3(nb), dim3(256), 0, ctx->stream, ctx->L, ctx->S, E, ctx->d_codes,
-                           ctx->d_a8, ctx->d_a32, F.n_codes, chunk);
-        hipLaunchKernelGGL(k_explore_totals, dim3(1), dim3(EX_MAX_BLOCKS), 0, ctx->stream, E, nb, avail, ctx->d_ctr,
+        hipLaunchKernelGGL(k_explore_scan, dim3(g.nb), dim3(256), 0, ctx->stream, ctx->L, ctx->S, E, ctx->d_codes,
+                           ctx->d_a8, ctx->d_a32, F.n_codes, g.chunk);
+        hipLaunchKernelGGL(k_explore_totals, dim3(1), dim3(RK_MAX_BLOCKS), 0, ctx->stream, E, g.nb, avail, ctx->d_ctr,
                            n_step_ctr, ctx->d_ectr);
-        hipLaunchKernelGGL(k_explore_emit, dim3(tiles), dim3(256), 0, ctx->stream, E, n, N, chunk, used, avail);
+        hipLaunchKernelGGL(k_explore_emit, dim3(g.tiles), dim3(256), 0, ctx->stream, E, n, N, g.chunk, used, avail);
         HIPX(ctx, hipGetLastError());
         HIPX(ctx, hipMemcpyAsync(ctx->h_ectr, ctx->d_ectr, sizeof(ExploreCtr), hipMemcpyDeviceToHost, ctx->stream));
         HIPX(ctx, hipStreamSynchronize(ctx->stream));
@@ -1691,14 +1730,11 @@ extern "C" int mg_explore_download(mg_ctx *ctx, uint32_t *path, uint32_t *path_l
     if (!path || !path_len || !root) return set_err(ctx, MG_EINVAL, "mg_explore_download: path, path_len and root are required");
     HIPX(ctx, hipSetDevice(ctx->device));
     const DevExplore &E = ctx->E;
-    const size_t N = ctx->L.N, cap = E.path_cap;
-    std::vector<uint32_t> rows(cap * (size_t)n);
-    HIPX(ctx, hipStreamSynchronize(ctx->stream));
-    HIPX(ctx, hipMemcpy(path_len, E.path_len + first, (size_t)n * 4u, hipMemcpyDeviceToHost));
-    HIPX(ctx, hipMemcpy(root, E.root + first, (size_t)n * 4u, hipMemcpyDeviceToHost));
-    HIPX(ctx, hipMemcpy2D(rows.data(), (size_t)n * 4u, E.path + first, N * 4u, (size_t)n * 4u, cap, hipMemcpyDeviceToHost));
-    for (uint32_t i = 0; i < n; ++i)
-        for (size_t e = 0; e < cap; ++e) path[(size_t)i * cap + e] = e < path_len[i] ? rows[e * n + i] : 0u;
+    XferPlan x(n, first);
+    plan_paths(x, path, path_len, root, E, XB_ALL);
+    int rc;
+    if ((rc = xfer_down(ctx, x))) return rc;
+    zero_path_tails(path, path_len, n, E.path_cap, E.path_cap);
     return MG_OK;
 }
 
@@ -1711,18 +1747,18 @@ extern "C" int mg_explore_upload(mg_ctx *ctx, const uint32_t *path, const uint32
     if (n == 0u) return MG_OK;
     if (!path || !path_len || !root) return set_err(ctx, MG_EINVAL, "mg_explore_upload: path, path_len and root are required");
     const DevExplore &E = ctx->E;
-    const size_t N = ctx->L.N, cap = E.path_cap;
+    const size_t cap = E.path_cap;
     for (uint32_t i = 0; i < n; ++i)
         if (path_len[i] > cap)
             return set_err(ctx, MG_EINVAL, "mg_explore_upload: path_len[%u] = %u above path_cap %zu", i, path_len[i], cap);
     HIPX(ctx, hipSetDevice(ctx->device));
-    std::vector<uint32_t> rows(cap * (size_t)n);            // entry-major, as the plane; 0 above a lane's length
-    for (uint32_t i = 0; i < n; ++i)
-        for (size_t e = 0; e < cap; ++e) rows[e * n + i] = e < path_len[i] ? path[(size_t)i * cap + e] : 0u;
+    std::vector<uint32_t> rows(path, path + cap * (size_t)n);   // the plane receives 0 above a lane's length
+    zero_path_tails(rows.data(), path_len, n, cap, E.path_cap);
+    XferPlan x(n, first);                                       // the plan reads its host side only
+    plan_paths(x, rows.data(), const_cast<uint32_t *>(path_len), const_cast<uint32_t *>(root), E, XB_ALL);
+    int rc;
+    if ((rc = xfer_up(ctx, x))) return rc;
     HIPX(ctx, hipStreamSynchronize(ctx->stream));
-    HIPX(ctx, hipMemcpy(E.path_len + first, path_len, (size_t)n * 4u, hipMemcpyHostToDevice));
-    HIPX(ctx, hipMemcpy(E.root + first, root, (size_t)n * 4u, hipMemcpyHostToDevice));
-    HIPX(ctx, hipMemcpy2D(E.path + first, N * 4u, rows.data(), (size_t)n * 4u, (size_t)n * 4u, cap, hipMemcpyHostToDevice));
     return MG_OK;
 }
 
@@ -1738,33 +1774,18 @@ extern "C" int mg_harvest_select(mg_ctx *ctx, uint32_t status_mask, const uint32
     if (!ctx->uploaded) return set_err(ctx, MG_ESTATE, "mg_harvest_select before mg_lanes_upload");
     if (!info) return set_err(ctx, MG_EINVAL, "mg_harvest_select: info is null");
     const uint32_t n = ctx->L.n, N = ctx->L.N;
-    if (n_skip && !skip) return set_err(ctx, MG_EINVAL, "mg_harvest_select: skip is null with n_skip = %u", n_skip);
-    for (uint32_t j = 0; j < n_skip; ++j) {
-        if (skip[j] >= n)
-            return set_err(ctx, MG_EINVAL, "mg_harvest_select: skip[%u] = %u outside batch of %u", j, skip[j], n);
-        if (j && skip[j] <= skip[j - 1u])
-            return set_err(ctx, MG_EINVAL, "mg_harvest_select: skip[%u] = %u is not above skip[%u] = %u", j, skip[j],
-                           j - 1u, skip[j - 1u]);
-    }
+    int rc;
+    if ((rc = check_lane_list(ctx, "mg_harvest_select", "skip", skip, n_skip, n))) return rc;
     HIPX(ctx, hipSetDevice(ctx->device));
     DevHarvest &H = ctx->H;
-    int rc;
     if (!H.list) {                       // first use for this batch; freed with the lanes
         uint32_t *scratch = nullptr;     // skipm, skip, rank, list: [N] each; bt, boff; info
-        if ((rc = lane_alloc(ctx, scratch, (size_t)4u * N + 2u * HV_MAX_BLOCKS + 2u + HV_FIELDS))) return rc;
+        if ((rc = lane_alloc(ctx, scratch, (size_t)4u * N + 2u * RK_MAX_BLOCKS + 2u + HV_FIELDS))) return rc;
         H.skipm = scratch; H.skip = scratch + N; H.rank = scratch + 2u * (size_t)N; H.list = scratch + 3u * (size_t)N;
-        H.bt = scratch + 4u * (size_t)N; H.boff = H.bt + HV_MAX_BLOCKS; H.info = H.boff + HV_MAX_BLOCKS;
+        H.bt = scratch + 4u * (size_t)N; H.boff = H.bt + RK_MAX_BLOCKS; H.info = H.boff + RK_MAX_BLOCKS;
     }
     ctx->hv_valid = false;
-    // MG_HARVEST_BLOCKS caps the scan blocks (a small batch can then cross both the tile carry and the offsets)
-    uint32_t max_blocks = HV_MAX_BLOCKS;
-    if (const char *e = getenv("MG_HARVEST_BLOCKS")) {
-        const long v = strtol(e, nullptr, 10);
-        if (v >= 1 && v <= (long)HV_MAX_BLOCKS) max_blocks = (uint32_t)v;
-    }
-    const uint32_t tiles = blocks_for(n);
-    const uint32_t chunk = ((tiles + max_blocks - 1u) / max_blocks) * 256u;
-    const uint32_t nb = (n + chunk - 1u) / chunk;            // <= max_blocks
+    const RankGeometry g = rank_geometry(n, rank_max_blocks("MG_HARVEST_BLOCKS"));
     const size_t info_off = ((size_t)n_skip * 4u + 15u) & ~(size_t)15u, info_bytes = (2u + HV_FIELDS) * 4u;
     if ((rc = ensure_hxfer(ctx, info_off + info_bytes))) return rc;
     HIPX(ctx, hipMemsetAsync(H.skipm, 0, (size_t)n * 4u, ctx->stream));
@@ -1780,10 +1801,11 @@ extern "C" int mg_harvest_select(mg_ctx *ctx, uint32_t status_mask, const uint32
     C.f[7] = ctx->E.path ? ctx->E.path_len : nullptr;
     max_lanes = std::min(max_lanes, n);
     HIPX(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-    if (n_skip) hipLaunchKernelGGL(k_harvest_mark, dim3(blocks_for(n_skip)), dim3(256), 0, ctx->stream, H, n_skip);
-    hipLaunchKernelGGL(k_harvest_scan, dim3(nb), dim3(256), 0, ctx->stream, H, L.status, n, status_mask, chunk);
-    hipLaunchKernelGGL(k_harvest_totals, dim3(1), dim3(HV_MAX_BLOCKS), 0, ctx->stream, H, nb, max_lanes);
-    hipLaunchKernelGGL(k_harvest_emit, dim3(tiles), dim3(256), 0, ctx->stream, H, C, n, chunk, max_lanes);
+    if (n_skip)
+        hipLaunchKernelGGL(k_lane_mark, dim3(blocks_for(n_skip)), dim3(256), 0, ctx->stream, H.skipm, H.skip, n_skip);
+    hipLaunchKernelGGL(k_harvest_scan, dim3(g.nb), dim3(256), 0, ctx->stream, H, L.status, n, status_mask, g.chunk);
+    hipLaunchKernelGGL(k_harvest_totals, dim3(1), dim3(RK_MAX_BLOCKS), 0, ctx->stream, H, g.nb, max_lanes);
+    hipLaunchKernelGGL(k_harvest_emit, dim3(g.tiles), dim3(256), 0, ctx->stream, H, C, n, g.chunk, max_lanes);
     HIPX(ctx, hipGetLastError());
     HIPX(ctx, hipEventRecord(ctx->ev1, ctx->stream));
     HIPX(ctx, hipMemcpyAsync(ctx->h_xfer + info_off, H.info, info_bytes, hipMemcpyDeviceToHost, ctx->stream));
@@ -1834,27 +1856,19 @@ extern "C" int mg_harvest_download(mg_ctx *ctx, uint32_t *lanes, mg_lane_soa *h,
                        true};
     XferPlan x(n, ctx->H.list);
     // one phase, scalars first: k_xfer_pick takes their stage offsets as 32-bit words, and at
-    // most XP_MAX of them (19 of the lanes, 2 symbolic, 2 of the path; xfer_down refuses more)
+    // most XP_MAX of them (19 of the lanes, 2 symbolic, 2 of the path; xfer_down refuses more);
+    // the path rows, the smallest, follow their scalars
     x.scalar(lanes, ctx->H.list, 4);     // the list itself: copied, not picked (xfer_down)
     plan_lane_scalars(x, h, L, nullptr);
     if (sym) plan_sym_scalars(x, sym, S);
-    if (path) {
-        x.scalar(path_len, E.path_len, 4);
-        x.scalar(root, E.root, 4);
-    }
+    const uint32_t b_path = std::min(I.path_len, E.path_cap);
+    if (path) plan_paths(x, path, path_len, root, E, b_path);
     plan_lane_rows(x, h, L, b, nullptr);
     if (sym)
         plan_sym_rows(x, sym, S, SymBounds{b_sp, std::min(I.n_nodes, S.node_cap), std::min(I.n_consts, S.const_cap),
                                            b_ms, b_st});
-    const uint32_t b_path = path ? std::min(I.path_len, E.path_cap) : 0u;
-    if (path) x.units(path, E.path_cap, 1, E.path, b_path);
     if ((rc = xfer_down(ctx, x))) return rc;
-    if (path) {
-        // the plane above a lane's path_len holds what an earlier owner of the lane left
-        const size_t cap = E.path_cap;
-        for (uint32_t i = 0; i < n; ++i)
-            for (size_t e = std::min(path_len[i], b_path); e < cap; ++e) path[(size_t)i * cap + e] = 0u;
-    }
+    if (path) zero_path_tails(path, path_len, n, E.path_cap, b_path);
     return MG_OK;
 }
 

@@ -7,7 +7,9 @@ a. one round equals dev.step() + a full download + exploremodel.plan + dev.fork 
    go wrong: three blocks, sources on the wave and block edges, a dense run over a
    block edge, free lanes between and above the sources, an invalid target, a
    taint lane and a symbolic-target lane inside the run, and a free list that is
-   exact, one short and empty; at 64 and 32 lanes per wave of kernel 1;
+   exact, one short and empty; at 64 and 32 lanes per wave of kernel 1; and with
+   the scan blocks capped at 1 and 2, so that the ranks cross the carry over a
+   block's tiles and the block offsets;
 b. R rounds in one call equal R calls of one round, each given the unused tail of
    the free list: the image, the paths (composed through root) and the summed stats;
 c. co-simulation against the CPU restatement (tests/symref.py), both sides
@@ -113,7 +115,23 @@ def _hand_image(n, cid, rng):
 @pytest.mark.parametrize("short", [0, 1, None], ids=["exact", "one-short", "no-free-lane"])
 @pytest.mark.parametrize("layout", ["between", "above"])
 def test_one_round_equals_step_plus_planned_fork(dev_lpw, layout, short):
-    dev = dev_lpw
+    _one_round(dev_lpw, layout, short)
+
+
+@pytest.mark.parametrize("short", [0, 1], ids=["exact", "one-short"])
+@pytest.mark.parametrize("blocks", ["1", "2"], ids=["blocks1", "blocks2"])
+def test_one_round_across_the_tile_carry_and_the_block_offsets(dev, monkeypatch, blocks, short):
+    """The same round with the plan's scan blocks capped (MG_EXPLORE_BLOCKS, read per
+    call): the 600 lanes are three tiles, the last partial.  With 1 a single block owns
+    all three and both ranked classes carry over its tile edges (the in-place source is
+    lane 254, the dense run 250-260 straddles the first edge); with 2 there are a
+    two-tile and a one-tile block, so the carry and the block offsets work together.
+    The model's plan knows nothing of blocks."""
+    monkeypatch.setenv("MG_EXPLORE_BLOCKS", blocks)
+    _one_round(dev, "between", short, f"MG_EXPLORE_BLOCKS={blocks}, ")
+
+
+def _one_round(dev, layout, short, note=""):
     n, free = _layout(layout)
     assert len(free) >= NEED and NEED == 14
     free = [] if short is None else free[:NEED - short]
@@ -155,7 +173,7 @@ def test_one_round_equals_step_plus_planned_fork(dev_lpw, layout, short):
     # the starved, the taint and the symbolic-target lanes are as the step left them
     still = list(starved) + [TAINT, SYMTARGET]
     assert whole_diff(left, img, lanes=still) == [] and (left.status[still] == MG_FORK).all()
-    print(f"{layout}, {len(free)} free: {st.forks} forks, {st.made_jump} jump lanes, {st.starved} starved, "
+    print(f"{note}{layout}, {len(free)} free: {st.forks} forks, {st.made_jump} jump lanes, {st.starved} starved, "
           f"kernel_ms {st.kernel_ms:.4f}")
 
 

@@ -20,9 +20,12 @@ d. symbolic and taint lanes stepped on dirty planes equal the same lanes on
    the zeroed planes of a new allocation;
 e. every documented refusal leaves the device image and the context intact,
    NULL fields are skipped on download, and a live download refuses a NULL
-   count array whose rows are requested.
+   count array whose rows are requested;
+f. the path planes (mg_explore_upload, mg_explore_download): ranges inside and
+   across tiles, zeros at and above path_len in both directions, the refusals.
 """
 import ctypes
+import dataclasses
 from copy import copy
 
 import numpy as np
@@ -537,3 +540,102 @@ def test_null_fields_and_live_counts(dev):
         getattr(want, rows)[...] = getattr(keep, rows)
         assert whole_diff(got, want) == [], count
     assert whole_diff(_full(dev, shape), _expected_full(model)) == []
+
+
+# ------------------------------------------------ f. the path planes of mg_explore
+PATH_RANGES = [(0, 600), (63, 130), (560, 40), (599, 1)]
+SENTINEL = 0xA5A5A5A5
+
+
+def _paths_down(dev, cap, first, n):
+    """mg_explore_download into sentinel-filled arrays: (rc, path, path_len, root)."""
+    path = np.full((n, cap), SENTINEL, dtype=np.uint32)
+    path_len, root = np.full(n, SENTINEL, dtype=np.uint32), np.full(n, SENTINEL, dtype=np.uint32)
+    rc = dev.lib.mg_explore_download(dev.ctx, path.ctypes.data, path_len.ctypes.data, root.ctypes.data, first, n)
+    return rc, path, path_len, root
+
+
+def _masked(path, path_len):
+    """The rows with 0 at and above each lane's length."""
+    keep = np.arange(path.shape[1])[None, :] < path_len[:, None]
+    return np.where(keep, path, 0).astype(np.uint32)
+
+
+def _model_rows(p):
+    """[path with 0 at and above each length, path_len, root] of a model's paths, copied."""
+    return [_masked(p.path, p.path_len), p.path_len.copy(), p.root.copy()]
+
+
+def test_path_planes_ranges_tails_and_refusals(dev):
+    """mg_explore_upload and mg_explore_download on the harvest tests' batch: 600
+    lanes (nine 64-lane transfer tiles and a tail of 24), path_cap 7, every length
+    0 .. 7."""
+    import test_gpu_harvest as harvest
+    n, cap = harvest.N, harvest.HPATH_CAP
+    _, _, built = harvest._batch(dev, "explore")                 # uploads its paths; left unchanged here
+    assert (n, cap) == (600, 7) and set(built.path_len.tolist()) == set(range(cap + 1))
+    lib, ctx = dev.lib, dev.ctx
+    want = _model_rows(built)
+
+    def check_ranges(what):
+        for first, k in PATH_RANGES:
+            rc, path, path_len, root = _paths_down(dev, cap, first, k)
+            assert rc == native.MG_OK, lib.mg_last_error(ctx)
+            assert np.array_equal(path_len, want[1][first:first + k]), (what, first, k)
+            assert np.array_equal(root, want[2][first:first + k]), (what, first, k)
+            assert np.array_equal(path, want[0][first:first + k]), (what, first, k)
+            # at and above path_len: 0, whatever the host array held
+            assert not (path[np.arange(cap)[None, :] >= path_len[:, None]]).any(), (what, first, k)
+
+    check_ranges("as uploaded")
+    # a sub-range with other rows: the lanes outside it keep theirs
+    first, k = 64, 65
+    rng = np.random.default_rng(0x9A7)
+    new_len = ((np.arange(k) * 3 + 5) % (cap + 1)).astype(np.uint32)
+    assert set(new_len.tolist()) == set(range(cap + 1))
+    new_path = _masked(rng.integers(1, 1 << 32, size=(k, cap), dtype=np.uint32), new_len)
+    new_root = rng.integers(0, n, size=k, dtype=np.uint32)
+    dev.explore_upload_paths(new_path, new_len, new_root, first)
+    want[0][first:first + k], want[1][first:first + k], want[2][first:first + k] = new_path, new_len, new_root
+    check_ranges("after the sub-range")
+    # junk above path_len on the host never reaches a reader: the range download and a
+    # harvest of those lanes at the full path capacity both return zeros there
+    junk = rng.integers(1, 1 << 32, size=(k, cap), dtype=np.uint32)
+    junk_len = new_len[::-1].copy()
+    dev.explore_upload_paths(junk, junk_len, new_root, first)
+    want[0][first:first + k], want[1][first:first + k] = _masked(junk, junk_len), junk_len
+    check_ranges("after the junk rows")
+    chosen = list(range(first, first + k))
+    info = dev.harvest_select(0xFFFFFFFF, sorted(set(range(n)) - set(chosen)))
+    assert info.n == k and info.path_len == cap
+    got = sentinel_filled(dataclasses.replace(dev.shape, n=k))
+    rc, lanes, path, path_len, root = harvest._download(dev, got, True, cap)
+    assert rc == native.MG_OK and lanes.tolist() == chosen
+    assert np.array_equal(path, want[0][first:first + k]) and np.array_equal(path_len, junk_len)
+    assert np.array_equal(root, new_root)
+
+    # refusals keep their codes and move nothing
+    ok = [a.copy() for a in (new_path, new_len, new_root)]
+    ptr = lambda a: a.ctypes.data
+    for fn in (lib.mg_explore_upload, lib.mg_explore_download):
+        assert fn(ctx, ptr(ok[0]), ptr(ok[1]), ptr(ok[2]), n - k + 1, k) == native.MG_EINVAL       # past the batch
+        assert fn(ctx, ptr(ok[0]), ptr(ok[1]), ptr(ok[2]), n, 1) == native.MG_EINVAL
+        assert fn(ctx, ptr(ok[0]), ptr(ok[1]), ptr(ok[2]), 0xFFFFFFFF, 2) == native.MG_EINVAL
+        assert fn(ctx, None, ptr(ok[1]), ptr(ok[2]), first, k) == native.MG_EINVAL
+        assert fn(ctx, ptr(ok[0]), None, ptr(ok[2]), first, k) == native.MG_EINVAL
+        assert fn(ctx, ptr(ok[0]), ptr(ok[1]), None, first, k) == native.MG_EINVAL
+        assert fn(ctx, None, None, None, first, 0) == native.MG_OK                                 # nothing to move
+    long_len = new_len.copy()
+    long_len[k - 1] = cap + 1
+    assert lib.mg_explore_upload(ctx, ptr(ok[0]), ptr(long_len), ptr(ok[2]), first, k) == native.MG_EINVAL
+    assert b"path_len" in lib.mg_last_error(ctx)
+    assert all(np.array_equal(a, b) for a, b in zip(ok, (new_path, new_len, new_root)))
+    check_ranges("after the refusals")
+    # before mg_explore_alloc
+    harvest._forget(dev)
+    dev.alloc(_shape("symbolic", n=8))
+    small = [np.zeros((8, cap), dtype=np.uint32), np.zeros(8, dtype=np.uint32), np.zeros(8, dtype=np.uint32)]
+    for fn in (lib.mg_explore_upload, lib.mg_explore_download):
+        assert fn(ctx, ptr(small[0]), ptr(small[1]), ptr(small[2]), 0, 8) == native.MG_ESTATE
+        assert b"mg_explore_alloc" in lib.mg_last_error(ctx)
+
