@@ -735,6 +735,50 @@ int         mg_harvest_select(mg_ctx *ctx, uint32_t status_mask, const uint32_t 
 int         mg_harvest_download(mg_ctx *ctx, uint32_t *lanes /* [n] */, mg_lane_soa *host /* host->n == n */,
                                 mg_sym_soa *sym /* or NULL */, uint32_t *path /* [n][path_cap] or NULL */,
                                 uint32_t *path_len, uint32_t *root /* both NULL iff path is NULL */);
+/* mg_harvest_upload, the inverse of mg_harvest_download: lanes the host has resolved
+ * (escapes, hooks) go back into a running batch by list.  Row i of every host array
+ * goes to device lane lanes[i], n = host->n rows.  lanes is strictly ascending with
+ * every entry below n_lanes; lanes == NULL means the resident list of the last
+ * mg_harvest_select ("take out, resolve, put back where it was": no list crosses
+ * PCIe), MG_ESTATE without a selection, MG_EINVAL when host->n != its info.n.
+ * What is written.  The scalars of mg_lanes_upload, whole; fent is the host's, or
+ * 0xffffffff when host->fent is NULL; trace_len / rec_len are the host's, or 0 when
+ * the host's trace_cap / rec_cap is 0; sha3_count and exp_count are 0: a planted lane
+ * is what mg_lanes_upload of a range would leave.  calldata (up to the host's
+ * calldata_cap) and the environment words go whole.  Rows go below the LARGEST COUNT
+ * AMONG THE n HOST ROWS, clipped to the host capacities: stack below the largest sp,
+ * memory below the largest msize, storage below the largest storage_count, trace and
+ * records below the largest trace_len / rec_len.  With sym (sym->n == n): n_nodes and
+ * n_consts, node below the largest n_nodes, cval below the largest n_consts, stag
+ * below the largest sp, mtag below the largest msize, sttag below the largest
+ * storage_count -- the live extent mg_harvest_download and the device fork use, not
+ * the full-capacity tag planes of mg_sym_upload.  With path (path, path_len and root
+ * all given): path_len, root, and path rows below the largest path_len of the call;
+ * entries at and above a lane's own path_len arrive as 0 (the host's are not read).
+ * What is not written: unlisted lanes; cells at and above a bound; the resident
+ * reset image (a later mg_lanes_reset gives a planted lane the pc, depth, status,
+ * aux, steps, gas and storage the image holds for that lane, under the planted
+ * code_id, flags, inputs and gas limit); coverage; the explorer's free marks; the
+ * resident selection; the symbolic planes when sym is NULL and the path planes when
+ * path is NULL.  Taint planes are not part of the call.
+ * Every check runs on the host before any copy or launch, and a refused call leaves
+ * the image as it was.  MG_ESTATE: no batch, or no earlier mg_lanes_upload.
+ * MG_EINVAL: a NULL host; a list that is not strictly ascending below n_lanes (the
+ * message names the index); host capacities above the batch's; sym->n != n; sym
+ * without symbolic planes; path without explore planes; path / path_len / root not
+ * given together; a row whose sp, msize, calldata_len, storage_count, trace_len,
+ * rec_len, n_nodes or n_consts is above its host capacity, whose msize is not a
+ * multiple of 32 or whose path_len is above path_cap.  MG_ENOCODE: a row with an
+ * unknown code_id.  Row messages name the device lane (the row, for the resident
+ * list).  Accepted code ids count as used for the stepping kernel's code plan.
+ * n == 0 succeeds and does nothing.
+ * Cost: one H2D copy (list, scalars and rows in one stage), one stream
+ * synchronisation, and numbers of launches and copies that depend on the fields
+ * present, never on n or on how the list is spread over the batch.              */
+int         mg_harvest_upload(mg_ctx *ctx, const uint32_t *lanes /* [n], or NULL */,
+                              const mg_lane_soa *host /* n = host->n */, const mg_sym_soa *sym /* or NULL */,
+                              const uint32_t *path /* [n][path_cap] or NULL */, const uint32_t *path_len,
+                              const uint32_t *root /* both NULL iff path is NULL */);
 
 /* The fork filter's question, "does any cached model satisfy this lane's path"
  * (svm.py:319-326 -> ModelCache.check_quick_sat, support_utils.py:60-68), answered

@@ -21,6 +21,10 @@
 // host never passes a count above the n that k_harvest_totals reported, and the
 // list lives as long as the planes it indexes (mg_lanes_alloc, mg_sym_alloc and
 // mg_explore_alloc drop the selection).
+//
+// mg_harvest_upload is the way back: k_xfer_place (below) and mythgpu.hip's
+// k_xfer_scatter_idx write the listed lanes from the stage.  Their list is the resident
+// one or the caller's, which the host checked with check_lane_list before any launch.
 #pragma once
 
 #define HV_NONE 0xffffffffu     // rank of a lane that does not match
@@ -108,4 +112,28 @@ __global__ __launch_bounds__(256) void k_xfer_pick(PickTable P, const uint32_t *
     const uint32_t lane = list[i];                           // < n_lanes (the invariant above)
     if (P.elem[f] == 8u) ((uint64_t *)(dst + P.off[f]))[i] = ((const uint64_t *)P.src[f])[lane];
     else ((uint32_t *)(dst + P.off[f]))[i] = ((const uint32_t *)P.src[f])[lane];
+}
+
+// ---- indexed placement (mg_harvest_upload): the inverse of k_xfer_pick ------------
+// An entry with elem 4 or 8 copies stage element i to dst[list[i]]; an entry with elem 0
+// is a fill: dst[list[i]] = off, a 4-byte constant (what the host does not supply
+// starts clean, and a memset cannot follow a list).  At most XP_MAX copies and
+// XP_FILL_MAX fills per launch.
+#define XP_FILL_MAX 8u
+struct PlaceTable {
+    void *dst[XP_MAX + XP_FILL_MAX];
+    uint32_t off[XP_MAX + XP_FILL_MAX];     // byte offset of the field in the stage; a fill's value
+    uint32_t elem[XP_MAX + XP_FILL_MAX];    // 4 or 8; 0: a fill
+};
+
+// blockIdx.y = entry; src is 16-byte aligned and so is every off.  Every list entry is
+// below n_lanes: the host checked it (check_lane_list) or k_harvest_emit wrote it.
+__global__ __launch_bounds__(256) void k_xfer_place(PlaceTable P, const uint32_t *__restrict__ list, uint32_t n,
+                                                    const uint8_t *__restrict__ src) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, f = blockIdx.y;
+    if (i >= n) return;
+    const uint32_t lane = list[i];
+    if (P.elem[f] == 8u) ((uint64_t *)P.dst[f])[lane] = ((const uint64_t *)(src + P.off[f]))[i];
+    else if (P.elem[f] == 4u) ((uint32_t *)P.dst[f])[lane] = ((const uint32_t *)(src + P.off[f]))[i];
+    else ((uint32_t *)P.dst[f])[lane] = P.off[f];
 }

@@ -647,6 +647,38 @@ __global__ __launch_bounds__(256) void k_xfer_gather_idx(const uint32_t *__restr
         if (l < nl && c < cols) dst[(size_t)(l0 + l) * row + ((size_t)u0 << lgW) + c] = tile[l][c];
     }
 }
+// k_xfer_scatter through a lane list (mg_harvest_upload): stage row l0 + l goes to device
+// lane list[l0 + l].  The stage side stays contiguous; the list ascends, so neighbouring
+// tile rows are neighbouring or near lanes and a unit's 64 stores fall into few lines.
+// Every entry is below n_lanes (the host checked the caller's list; k_harvest_emit wrote
+// the resident one), so the writes stay inside the plane as long as U is at most its
+// capacity.
+template <bool BSWAP>
+__global__ __launch_bounds__(256) void k_xfer_scatter_idx(const uint32_t *__restrict__ src, uint32_t n, uint32_t U,
+                                                         uint32_t lgW, uint32_t *__restrict__ dst, uint32_t N,
+                                                         const uint32_t *__restrict__ list) {
+    __shared__ uint32_t tile[XT_LANES][XT_COLS + 1];
+    __shared__ uint32_t lane_of[XT_LANES];
+    const uint32_t W = 1u << lgW, TU = XT_COLS >> lgW;
+    const uint32_t l0 = blockIdx.x * XT_LANES, u0 = blockIdx.y * TU;
+    const uint32_t nl = min(XT_LANES, n - l0), nu = min(TU, U - u0), cols = nu << lgW;
+    const size_t row = (size_t)U << lgW;
+    if (threadIdx.x < nl) lane_of[threadIdx.x] = list[l0 + threadIdx.x];
+    for (uint32_t i = threadIdx.x; i < XT_LANES * XT_COLS; i += blockDim.x) {
+        const uint32_t l = i / XT_COLS, c = i % XT_COLS;
+        if (l < nl && c < cols) {
+            const uint32_t v = src[(size_t)(l0 + l) * row + ((size_t)u0 << lgW) + c];
+            tile[l][c] = BSWAP ? __builtin_bswap32(v) : v;
+        }
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < XT_LANES * XT_COLS; i += blockDim.x) {
+        const uint32_t uo = i / (XT_LANES * W), rem = i % (XT_LANES * W);
+        const uint32_t l = rem >> lgW, k = rem & (W - 1u);
+        if (uo < nu && l < nl)
+            dst[(((size_t)(u0 + uo) * N + lane_of[l]) << lgW) + k] = tile[l][(uo << lgW) + k];
+    }
+}
 static uint32_t lg2(uint32_t w) { uint32_t r = 0; while ((1u << r) < w) ++r; return r; }
 static dim3 xfer_grid(uint32_t n, uint32_t U, uint32_t W) {
     return dim3((n + XT_LANES - 1) / XT_LANES, (U + (XT_COLS / W) - 1) / (XT_COLS / W));
@@ -692,9 +724,15 @@ struct XferPlan {
     bool bad = false;           // a field the transfer kernels cannot move
     size_t total = 0;
     uint32_t n = 0, first = 0;
-    const uint32_t *list = nullptr;     // download only: stage row i is device lane list[i], not first + i
+    const uint32_t *list = nullptr;     // stage row i is device lane list[i], not first + i
+    // upload with a list: list == nullptr takes it from the stage, where the caller's list is
+    // the plan's first item (a scalar without a device side); dev2 is never used; fills are
+    // the constants k_xfer_place writes to the listed lanes of a field the host does not supply
+    bool indexed = false;
+    struct Fill { void *dev; uint32_t value; };
+    std::vector<Fill> fills;
     XferPlan(uint32_t n_, uint32_t first_) : n(n_), first(first_) {}
-    XferPlan(uint32_t n_, const uint32_t *list_) : n(n_), list(list_) {}
+    XferPlan(uint32_t n_, const uint32_t *list_) : n(n_), list(list_), indexed(true) {}
     void add(Item it) {
         if (!it.host) return;
         if (it.kind == SCALAR) it.len = (size_t)n * it.elem;
@@ -820,8 +858,36 @@ static int xfer_up(mg_ctx *ctx, const XferPlan &x) {
         }
     }
     uint8_t *ds = (uint8_t *)ctx->d_stage;
-    HIPX(ctx, hipMemcpyAsync(ds, ctx->h_xfer, x.total, hipMemcpyHostToDevice, ctx->stream));
     const uint32_t N = ctx->L.N;
+    if (x.indexed) {
+        const uint32_t *list = x.list ? x.list : (const uint32_t *)ds;
+        // the scalars and the fills in one launch (a device-to-device copy or a memset cannot
+        // follow the list)
+        PlaceTable P{};
+        uint32_t np = 0;
+        for (const auto &it : x.items) {
+            if (it.kind != XferPlan::SCALAR || !it.dev) continue;
+            if (np == XP_MAX || (it.elem != 4 && it.elem != 8) || it.off > 0xffffffffu)
+                return set_err(ctx, MG_EINVAL, "lane transfer: scalar fields of an indexed upload");
+            P.dst[np] = it.dev; P.off[np] = (uint32_t)it.off; P.elem[np] = (uint32_t)it.elem;
+            ++np;
+        }
+        if (x.fills.size() > XP_FILL_MAX) return set_err(ctx, MG_EINVAL, "lane transfer: fills of an indexed upload");
+        for (const auto &f : x.fills) { P.dst[np] = f.dev; P.off[np] = f.value; P.elem[np] = 0u; ++np; }
+        HIPX(ctx, hipMemcpyAsync(ds, ctx->h_xfer, x.total, hipMemcpyHostToDevice, ctx->stream));
+        if (np) hipLaunchKernelGGL(k_xfer_place, dim3(blocks_for(x.n), np), dim3(256), 0, ctx->stream, P, list, x.n, ds);
+        for (const auto &it : x.items) {
+            if (it.kind == XferPlan::UNITS)
+                hipLaunchKernelGGL(k_xfer_scatter_idx<false>, xfer_grid(x.n, it.Uc, it.W), dim3(256), 0, ctx->stream,
+                                   (const uint32_t *)(ds + it.off), x.n, it.Uc, lg2(it.W), (uint32_t *)it.dev, N, list);
+            else if (it.kind == XferPlan::BYTES)
+                hipLaunchKernelGGL(k_xfer_scatter_idx<true>, xfer_grid(x.n, it.Uc, 1), dim3(256), 0, ctx->stream,
+                                   (const uint32_t *)(ds + it.off), x.n, it.Uc, 0u, (uint32_t *)it.dev, N, list);
+        }
+        HIPX(ctx, hipGetLastError());
+        return MG_OK;
+    }
+    HIPX(ctx, hipMemcpyAsync(ds, ctx->h_xfer, x.total, hipMemcpyHostToDevice, ctx->stream));
     for (const auto &it : x.items) {
         for (void *dev : {it.dev, it.dev2}) {
             if (!dev) continue;
@@ -1869,6 +1935,88 @@ extern "C" int mg_harvest_download(mg_ctx *ctx, uint32_t *lanes, mg_lane_soa *h,
                                            b_ms, b_st});
     if ((rc = xfer_down(ctx, x))) return rc;
     if (path) zero_path_tails(path, path_len, n, E.path_cap, b_path);
+    return MG_OK;
+}
+
+// The inverse: one stage (the caller's list, the scalars, the rows), one H2D copy, one
+// k_xfer_place and one k_xfer_scatter_idx per row field, one synchronisation.  The reset
+// image, coverage, the free marks and the selection are not touched.
+extern "C" int mg_harvest_upload(mg_ctx *ctx, const uint32_t *lanes, const mg_lane_soa *h, const mg_sym_soa *sym,
+                                 const uint32_t *path, const uint32_t *path_len, const uint32_t *root) {
+    if (!ctx) return MG_EINVAL;
+    if (!ctx->have_lanes) return set_err(ctx, MG_ESTATE, "mg_harvest_upload before mg_lanes_alloc");
+    if (!ctx->uploaded) return set_err(ctx, MG_ESTATE, "mg_harvest_upload before mg_lanes_upload");
+    DevLanes &L = ctx->L;
+    const DevSym &S = ctx->S;
+    const DevExplore &E = ctx->E;
+    if (!h) return set_err(ctx, MG_EINVAL, "mg_harvest_upload: host image is null");
+    const uint32_t n = h->n;
+    int rc;
+    if (!lanes) {
+        if (!ctx->hv_valid)
+            return set_err(ctx, MG_ESTATE, "mg_harvest_upload: no selection (mg_harvest_select first; an alloc drops it)");
+        if (n != ctx->hv.n)
+            return set_err(ctx, MG_EINVAL, "mg_harvest_upload: host image of %u lanes for a selection of %u", n, ctx->hv.n);
+    } else if ((rc = check_lane_list(ctx, "mg_harvest_upload", "lanes", lanes, n, L.n))) {
+        return rc;
+    }
+    if ((rc = check_host_caps(ctx, h))) return rc;
+    if (sym) {
+        if (!S.node) return set_err(ctx, MG_EINVAL, "mg_harvest_upload: sym given without symbolic planes (mg_sym_alloc)");
+        if (sym->n != n)
+            return set_err(ctx, MG_EINVAL, "mg_harvest_upload: symbolic host image of %u lanes for %u rows", sym->n, n);
+        if ((rc = check_sym_caps(ctx, sym))) return rc;
+    }
+    if (path && !E.path) return set_err(ctx, MG_EINVAL, "mg_harvest_upload: path given without explore planes (mg_explore_alloc)");
+    if ((path != nullptr) != (path_len != nullptr) || (path != nullptr) != (root != nullptr))
+        return set_err(ctx, MG_EINVAL, "mg_harvest_upload: path, path_len and root go together");
+    if (n == 0u) return MG_OK;
+    // lanes_upload's checks per row; the resident list is not on the host, so its rows are named
+    const char *what = lanes ? "lane" : "row";
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t at = lanes ? lanes[i] : i;
+        if (h->code_id[i] >= ctx->codes.size()) return set_err(ctx, MG_ENOCODE, "mg_harvest_upload: %s %u: unknown code_id", what, at);
+        if (h->sp[i] > h->stack_cap || h->msize[i] > h->mem_cap || h->msize[i] % 32 ||
+            h->calldata_len[i] > h->calldata_cap || h->storage_count[i] > h->storage_cap ||
+            (h->trace_cap ? h->trace_len[i] > h->trace_cap : 0u) || (h->rec_cap ? h->rec_len[i] > h->rec_cap : 0u))
+            return set_err(ctx, MG_EINVAL, "mg_harvest_upload: %s %u: state exceeds its host capacities", what, at);
+        if (sym && (sym->n_nodes[i] > sym->node_cap || sym->n_consts[i] > sym->const_cap))
+            return set_err(ctx, MG_EINVAL, "mg_harvest_upload: %s %u: arena exceeds its host capacities", what, at);
+        if (path && path_len[i] > E.path_cap)
+            return set_err(ctx, MG_EINVAL, "mg_harvest_upload: %s %u: path_len %u above path_cap %u", what, at, path_len[i],
+                           E.path_cap);
+    }
+    HIPX(ctx, hipSetDevice(ctx->device));
+    if (ctx->code_used.size() < ctx->codes.size()) ctx->code_used.resize(ctx->codes.size(), 0);
+    for (uint32_t i = 0; i < n; ++i) ctx->code_used[h->code_id[i]] = 1;
+    // the live extent: the largest count among the rows (the plan clips to the host capacities)
+    const uint32_t b_sp = max_of(h->sp, n), b_ms = max_of(h->msize, n), b_st = max_of(h->storage_count, n);
+    const LaneBounds b{b_sp, (b_ms + 3u) / 4u, b_st, h->trace_cap ? max_of(h->trace_len, n) : 0u,
+                       h->rec_cap ? max_of(h->rec_len, n) : 0u, true};
+    XferPlan x(n, lanes ? nullptr : ctx->H.list);
+    // one phase, the list and the scalars first: k_xfer_place takes stage offsets as 32-bit
+    // words and at most XP_MAX of them (19 of the lanes, 2 symbolic, 2 of the path)
+    if (lanes) x.scalar(const_cast<uint32_t *>(lanes), nullptr, 4);      // read from the stage, offset 0
+    plan_lane_scalars(x, h, L, nullptr);
+    // what the host does not supply starts clean
+    x.fills.push_back({L.sha3_count, 0u});
+    x.fills.push_back({L.exp_count, 0u});
+    if (!h->trace_cap) x.fills.push_back({L.trace_len, 0u});
+    if (!h->rec_cap) x.fills.push_back({L.rec_len, 0u});
+    if (!h->fent) x.fills.push_back({L.fent, MG_FENT_NONE});
+    if (sym) plan_sym_scalars(x, sym, S);
+    std::vector<uint32_t> rows;                                          // the plane receives 0 above a lane's length
+    if (path) {
+        rows.assign(path, path + (size_t)E.path_cap * n);
+        zero_path_tails(rows.data(), path_len, n, E.path_cap, E.path_cap);
+        plan_paths(x, rows.data(), const_cast<uint32_t *>(path_len), const_cast<uint32_t *>(root), E,
+                   max_of(path_len, n));
+    }
+    plan_lane_rows(x, h, L, b, nullptr);
+    if (sym)
+        plan_sym_rows(x, sym, S, SymBounds{b_sp, max_of(sym->n_nodes, n), max_of(sym->n_consts, n), b_ms, b_st});
+    if ((rc = xfer_up(ctx, x))) return rc;
+    HIPX(ctx, hipStreamSynchronize(ctx->stream));
     return MG_OK;
 }
 

@@ -319,6 +319,34 @@ class GpuDevice:
             root.ctypes.data if path is not None else None), "mg_harvest_download")
         return lanes, batch, path, path_len, root
 
+    def harvest_upload(self, lanes, batch: LaneBatch, path=None, path_len=None, root=None):
+        """mg_harvest_upload, the inverse of harvest_download: row i of `batch` (and of
+        path uint32[n, path_cap], path_len, root when given, all three or none) goes
+        to device lane lanes[i]; lanes strictly ascending, or None for the resident
+        list of the last harvest_select.  Only rows below the largest count among
+        the n rows cross PCIe; the symbolic planes go when the batch has them."""
+        n = batch.n
+        if lanes is not None:
+            lanes = np.ascontiguousarray(np.asarray(lanes, dtype=np.uint32).reshape(-1))
+            if lanes.size != n:
+                raise ValueError("harvest_upload: the host image has one lane per listed lane")
+        given = [a is not None for a in (path, path_len, root)]
+        if any(given) != all(given):
+            raise ValueError("harvest_upload: path, path_len and root go together")
+        if all(given):
+            path = np.ascontiguousarray(np.asarray(path, dtype=np.uint32))
+            path_len = np.ascontiguousarray(np.asarray(path_len, dtype=np.uint32).reshape(-1))
+            root = np.ascontiguousarray(np.asarray(root, dtype=np.uint32).reshape(-1))
+            if path.shape != (n, self.path_cap) or path_len.size != n or root.size != n:
+                raise ValueError("harvest_upload: path is [n, path_cap], path_len and root are [n]")
+        soa = batch.soa()
+        sym = batch.sym_soa_range(0, n) if batch.symbolic else None
+        self._check(self.lib.mg_harvest_upload(
+            self.ctx, lanes.ctypes.data if lanes is not None else None, ctypes.addressof(soa),
+            ctypes.addressof(sym) if sym is not None else None,
+            path.ctypes.data if path is not None else None, path_len.ctypes.data if path is not None else None,
+            root.ctypes.data if path is not None else None), "mg_harvest_upload")
+
     def harvest(self, status_mask: int, skip=(), max_lanes: Optional[int] = None, shape: Optional[LaneShape] = None):
         """harvest_select + harvest_download: (info, lanes, LaneBatch, path, path_len, root)."""
         info = self.harvest_select(status_mask, skip, max_lanes)

@@ -184,6 +184,7 @@ SIGNATURES = {
     "mg_explore_resume": (_I, [_P, _P, _U32, _U32, _U32, _P, _U32, ctypes.POINTER(MgExploreStats)]),
     "mg_harvest_select": (_I, [_P, _U32, _P, _U32, _U32, ctypes.POINTER(MgHarvestInfo)]),
     "mg_harvest_download": (_I, [_P, _P, _P, _P, _P, _P, _P]),
+    "mg_harvest_upload": (_I, [_P, _P, _P, _P, _P, _P, _P]),
     "mg_explore_download": (_I, [_P, _P, _P, _P, _U32, _U32]),
     "mg_explore_upload": (_I, [_P, _P, _P, _P, _U32, _U32]),
     "mg_explore_check": (_I, [_P, ctypes.POINTER(MgModelBatch), _P, _U32, _P, _P, _U32, _U32, _P, _P,
