@@ -92,3 +92,23 @@ __device__ __forceinline__ void keccak_f1600(uint64_t st[25]) {
         st[0] ^= kKeccakRC[round];
     }
 }
+
+// Keccak-256 of 64 bytes given as 16 big-endian dwords (a mapping slot's
+// keccak(key . slot)): one block, state set directly: no length masks and no
+// second read of the input.  `h`: the hash as a 256-bit word's little-endian limbs.
+__device__ __forceinline__ void keccak64(const uint32_t (&din)[16], uint32_t (&h)[8]) {
+    uint64_t st[25];
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+        st[i] = (uint64_t)__builtin_bswap32(din[2 * i]) | ((uint64_t)__builtin_bswap32(din[2 * i + 1]) << 32);
+    st[8] = 0x01ull;                 // domain pad right after the 64 bytes
+#pragma unroll
+    for (int i = 9; i < 25; ++i) st[i] = 0ull;
+    st[16] = 0x80ull << 56;          // last byte of the 136-byte rate
+    keccak_f1600(st);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        h[7 - 2 * q] = __builtin_bswap32((uint32_t)st[q]);
+        h[6 - 2 * q] = __builtin_bswap32((uint32_t)(st[q] >> 32));
+    }
+}

@@ -206,19 +206,20 @@ DEV int mem_extend(const U256 &start, const U256 &size, uint32_t &msize, uint64_
     return MX_OK;
 }
 
-// The fast loop's MLOAD / MSTORE: can the 32 bytes at `a` be accessed without the
-// general handler?  Yes inside msize (fee 0), and when the access grows memory to
-// `nms` bytes that still lie inside the LDS window and mem_cap (`grow_lim` =
-// min(4 * mw, mem_cap)): the window is zero past msize, so the growth is only the
-// fee of mem_extend above.  There nw <= 255, so the fee is exact in 32 bits.
-DEV bool mem_fast(const U256 &a, uint32_t msize, uint32_t grow_lim, uint32_t &nms, uint32_t &fee) {
+// The fast loop's MLOAD / MSTORE / SHA3: can the `len` (32 or 64) bytes at `a` be
+// accessed without the general handler?  Yes inside msize (fee 0), and when the
+// access grows memory to `nms` bytes that still lie inside the LDS window and
+// mem_cap (`grow_lim` = min(4 * mw, mem_cap)): the window is zero past msize, so the
+// growth is only the fee of mem_extend above.  There nw <= 255, so the fee is exact
+// in 32 bits.
+DEV bool mem_fast(const U256 &a, uint32_t len, uint32_t msize, uint32_t grow_lim, uint32_t &nms, uint32_t &fee) {
     nms = msize;
     fee = 0u;
     if (!u_fits32(a)) return false;
     const uint32_t off = a.w[0];
-    if (msize >= 32u && off <= msize - 32u) return true;
+    if (msize >= len && off <= msize - len) return true;
     if (off >= grow_lim) return false;                   // grow_lim <= 255 * 32: no wrap below
-    const uint32_t nw = (off + 63u) >> 5, ow = msize >> 5;
+    const uint32_t nw = (off + len + 31u) >> 5, ow = msize >> 5;
     if (nw * 32u > grow_lim) return false;
     nms = nw * 32u;
     fee = 3u * (nw - ow) + (nw * nw) / 512u - (ow * ow) / 512u;
@@ -382,8 +383,12 @@ struct LaneRegs {
     uint32_t pc, sp, msize, depth;
     uint32_t n_sha3, n_exp;
     uint32_t stop, sx;           // out: MG_RUNNING or the stop status and its aux word
-    uint32_t step;               // instructions this launch executed before this one
+    uint32_t step;               // instructions the lane executed before this one (L.steps + this launch's)
     uint32_t fent;               // last JUMP / JUMPI landing on a function entry (L.fent)
+    // the lane's counts: copies of L.rec_len, L.storage_count and L.calldata_len.  A
+    // handler that changes one stores it to memory too (write-through), so memory
+    // is current whenever the lane stops.
+    uint32_t rec_len, scnt, cdl;
 };
 // What the handlers read besides the registers (per lane / per block).
 // Per-wave Keccak result cache in LDS (SHA3 of 64 aligned bytes: a mapping
@@ -418,6 +423,130 @@ DEV uint32_t ktab_slot(const uint32_t (&u)[16]) {
 #pragma unroll
     for (int k = 0; k < 16; ++k) h = (h ^ u[k]) * 0x9e3779b1u;
     return (h >> 26) * KT_ENTRY;      // top 6 bits: KT_SLOTS = 64
+}
+
+// ---- SHA3 result lookup: the wave's LDS cache, then the context's table --------
+// Keccak cache: when every lane running this SHA3 finds its 64-byte aligned input
+// (`cacheable`, in `din`) among its wave's cached entries (e.g. balances[caller]
+// hashed again), the hashes come from LDS and Keccak-f is skipped; else all lanes
+// hash and the lowest uncached lane's result is inserted.  Exact 16-dword compare:
+// results are unchanged either way.  Both steps are called by all the lanes that
+// execute the SHA3 together: kc_lookup before hashing, kc_insert after it.
+struct KcProbe {
+    uint64_t act;        // the lanes running this SHA3
+    uint32_t *kt;        // the input's table entry when it is wave-uniform
+    uint32_t kt_state;
+    bool hit, all_hit;
+};
+// True when `res` holds the lane's hash (every lane hit the cache, or the table has the
+// wave's input); false: every lane hashes, whatever `res` holds.
+DEV bool kc_lookup(const StepEnv &E, bool cacheable, const uint32_t (&din)[16], U256 &res, KcProbe &P) {
+    uint32_t *kc = E.s_kc;
+    P.hit = false;
+    if (cacheable) {
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        const uint32_t valid = kc[KC_E * 24u];
+        for (uint32_t e = 0; e < KC_E; ++e) {
+            if (!((valid >> e) & 1u)) continue;
+            bool eq = true;
+#pragma unroll
+            for (int k = 0; k < 16; ++k) eq = eq && kc[e * 24u + k] == din[k];
+            if (eq && !P.hit) {
+                P.hit = true;
+#pragma unroll
+                for (int k = 0; k < 8; ++k) res.w[k] = kc[e * 24u + 16u + k];
+            }
+        }
+    }
+    P.act = __ballot(true);
+    P.all_hit = __ballot(P.hit) == P.act;
+    // Second level, on a miss: the context's table (device_state.h KT_*), for an
+    // input that is one value in every lane of this dispatch.
+    P.kt = nullptr;
+    P.kt_state = KT_BUSY;
+    bool tab_hit = false;
+    if (!P.all_hit && E.ktab != nullptr && __ballot(cacheable) == P.act) {
+        uint32_t u[16];
+        bool uni = true;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            u[k] = __builtin_amdgcn_readfirstlane(din[k]);
+            uni = uni && din[k] == u[k];
+        }
+        if (__ballot(uni) == P.act) {
+            P.kt = E.ktab + ktab_slot(u);
+            // agent-scope loads: vector loads served by L2, never the scalar cache
+#define KT_LOAD(p_) __hip_atomic_load((p_), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+            // the whole entry in one round trip (the loads are independent);
+            // res is overwritten by the caller unless the entry is taken
+            P.kt_state = KT_LOAD(P.kt + KT_STATE);
+            uint32_t diff = 0u;
+#pragma unroll
+            for (int k = 0; k < 16; ++k) diff |= KT_LOAD(P.kt + k) ^ u[k];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) res.w[k] = KT_LOAD(P.kt + 16 + k);
+            // usable: published by an earlier launch, and this input's
+            tab_hit = P.kt_state != 0u && P.kt_state < E.kepoch && diff == 0u;
+#undef KT_LOAD
+        }
+    }
+    return P.all_hit || tab_hit;
+}
+DEV void kc_insert(const StepEnv &E, bool cacheable, const uint32_t (&din)[16], const U256 &res, const KcProbe &P) {
+    if (P.all_hit) return;
+    uint32_t *kc = E.s_kc;
+    const uint64_t ins = __ballot(cacheable && !P.hit);
+    if (ins != 0ull && (uint32_t)__builtin_ctzll(ins) == (threadIdx.x & 63u)) {
+        const uint32_t e = kc[KC_E * 24u + 1u] % KC_E;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) kc[e * 24u + k] = din[k];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) kc[e * 24u + 16u + k] = res.w[k];
+        kc[KC_E * 24u] = kc[KC_E * 24u] | (1u << e);
+        kc[KC_E * 24u + 1u] = e + 1u;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    // a uniform input hashed here whose table slot read as free: the first active
+    // lane claims the slot and, if it wins, publishes the pair for later launches
+    if (P.kt != nullptr && P.kt_state == 0u && (uint32_t)__builtin_ctzll(P.act) == (threadIdx.x & 63u)) {
+        uint32_t expect = 0u;
+        if (__hip_atomic_compare_exchange_strong(P.kt + KT_STATE, &expect, KT_BUSY, __ATOMIC_RELAXED,
+                                                 __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
+#pragma unroll
+            for (int k = 0; k < 16; ++k) P.kt[k] = din[k];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) P.kt[16 + k] = res.w[k];
+            __hip_atomic_store(P.kt + KT_STATE, E.kepoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
+// The record payload of a 64-byte SHA3 input: its 16 dwords from `at` on.
+DEV void rec_din(const DevLanes &L, uint32_t lane, uint32_t at, const uint32_t (&din)[16]) {
+    uint32_t *rp = L.rec + lane + (size_t)at * L.N;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) rp[(size_t)k * L.N] = din[k];
+}
+
+// ---- storage lookup (account.py:43-74: first match wins) ------------------------
+// Index of the first of the lane's `cnt` entries whose key is `key`, or cnt.  The
+// first two entries are loaded together, one round trip (C2's lanes hold two);
+// kValue: with their values, and `val` is the found entry's value (zero if absent).
+template <bool kValue>
+DEV uint32_t storage_find(const LaneView &V, uint32_t cnt, const U256 &key, U256 &val) {
+    if (kValue) val = u_zero();
+    if (cnt == 0u) return 0u;
+    const g_u4 *st = gv(V.L.storage);
+    const size_t e0 = V.row(0u) * 2, e1 = V.row(cnt >= 2u ? 1u : 0u) * 2;
+    const U256 k0 = ld_word(st, e0), k1 = ld_word(st, e1);
+    U256 v0, v1;
+    if (kValue) { v0 = ld_word(st, e0 + 1); v1 = ld_word(st, e1 + 1); }
+    if (u_eq(k0, key)) { if (kValue) val = v0; return 0u; }
+    if (cnt >= 2u && u_eq(k1, key)) { if (kValue) val = v1; return 1u; }
+    for (uint32_t s = 2u; s < cnt; ++s) {
+        const size_t e = V.row(s) * 2;
+        if (u_eq(ld_word(st, e), key)) { if (kValue) val = ld_word(st, e + 1); return s; }
+    }
+    return cnt;
 }
 
 // Executes the instruction decoded as (uk, ux) for one lane, exactly as the
@@ -479,13 +608,13 @@ __device__ __forceinline__ void slow_step(LaneRegs &R, const StepEnv &E, uint32_
         switch (kind) {
         case K_ALU:
             if (op == 0x0a && L.rec_cap) {
-                rec_at = L.rec_len[lane];
+                rec_at = R.rec_len;
                 if (rec_at + MG_REC_HEADER + 16u > L.rec_cap) ESCX(MG_ESC_RECORD)
             }
             res = alu(op, a, b, c);
             if (op == 0x0a) {
                 ++R.n_exp;
-                if (L.rec_cap) rec_new = rec_exp(L, lane, rec_at, L.steps[lane] + R.step, res, a, b);
+                if (L.rec_cap) rec_new = rec_exp(L, lane, rec_at, R.step, res, a, b);
             }
             break;
         case K_PUSH:                                        // (:278-320)
@@ -525,7 +654,7 @@ __device__ __forceinline__ void slow_step(LaneRegs &R, const StepEnv &E, uint32_
             case 0x33: res = V.env(1); break;               // CALLER
             case 0x34: res = V.env(3); break;               // CALLVALUE
             case 0x3a: res = V.env(4); break;               // GASPRICE
-            case 0x36: res = u_small(L.calldata_len[lane]); break;
+            case 0x36: res = u_small(R.cdl); break;
             case 0x38: res = u_small(C.n_bytes); break;     // CODESIZE
             case 0x45: res = u_small(MG_MSTATE_GAS_LIMIT); break;
             case 0x58: res = u_small(a32[C.addr_off + pc]); break;
@@ -546,7 +675,7 @@ __device__ __forceinline__ void slow_step(LaneRegs &R, const StepEnv &E, uint32_
             if (ngmin >= glim) EXCX(MG_EXC_OUT_OF_GAS)
             MEMX(a, b, -1)
             if (b.w[0] != 0u && L.rec_cap) {
-                rec_at = L.rec_len[lane];
+                rec_at = R.rec_len;
                 if ((uint64_t)rec_at + MG_REC_HEADER + ((b.w[0] + 3u) >> 2) > L.rec_cap) ESCX(MG_ESC_RECORD)
             }
             ZEROFILL()
@@ -554,104 +683,25 @@ __device__ __forceinline__ void slow_step(LaneRegs &R, const StepEnv &E, uint32_
                 res.w[7] = 0xc5d24601u; res.w[6] = 0x86f7233cu; res.w[5] = 0x927e7db2u; res.w[4] = 0xdcc703c0u;
                 res.w[3] = 0xe500b653u; res.w[2] = 0xca82273bu; res.w[1] = 0x7bfad804u; res.w[0] = 0x5d85a470u;
             } else {
-                // Keccak cache: when every lane running this SHA3 finds its 64-byte
-                // aligned input among its wave's cached entries (e.g. balances[caller]
-                // hashed again), the hashes come from LDS and Keccak-f is skipped; else
-                // all lanes hash and the lowest uncached lane's result is inserted.
-                // Exact 16-dword compare: results are unchanged either way.
-                uint32_t *kc = E.s_kc;
+                // a mapping slot's shape (64 aligned bytes) goes through the wave's cache
+                // and the context's table (kc_lookup); every other shape hashes
                 const bool cacheable = b.w[0] == 64u && (a.w[0] & 3u) == 0u;
                 uint32_t din[16];
-                bool hit = false;
                 if (cacheable) {
 #pragma unroll
                     for (int k = 0; k < 16; ++k) din[k] = V.mdw_safe((a.w[0] >> 2) + (uint32_t)k);
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                    const uint32_t valid = kc[KC_E * 24u];
-                    for (uint32_t e = 0; e < KC_E; ++e) {
-                        if (!((valid >> e) & 1u)) continue;
-                        bool eq = true;
-#pragma unroll
-                        for (int k = 0; k < 16; ++k) eq = eq && kc[e * 24u + k] == din[k];
-                        if (eq && !hit) {
-                            hit = true;
-#pragma unroll
-                            for (int k = 0; k < 8; ++k) res.w[k] = kc[e * 24u + 16u + k];
-                        }
-                    }
                 }
-                const uint64_t act = __ballot(true);
-                const bool all_hit = __ballot(hit) == act;
-                // Second level, on a miss: the context's table (device_state.h KT_*), for an
-                // input that is one value in every lane of this dispatch.
-                uint32_t *kt = nullptr;           // the input's table entry when it is wave-uniform
-                uint32_t kt_state = KT_BUSY;
-                bool tab_hit = false;
-                if (!all_hit && E.ktab != nullptr && __ballot(cacheable) == act) {
-                    uint32_t u[16];
-                    bool uni = true;
-#pragma unroll
-                    for (int k = 0; k < 16; ++k) {
-                        u[k] = __builtin_amdgcn_readfirstlane(din[k]);
-                        uni = uni && din[k] == u[k];
-                    }
-                    if (__ballot(uni) == act) {
-                        kt = E.ktab + ktab_slot(u);
-                        // agent-scope loads: vector loads served by L2, never the scalar cache
-#define KT_LOAD(p_) __hip_atomic_load((p_), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                        // the whole entry in one round trip (the loads are independent);
-                        // res is overwritten below unless the entry is taken
-                        kt_state = KT_LOAD(kt + KT_STATE);
-                        uint32_t diff = 0u;
-#pragma unroll
-                        for (int k = 0; k < 16; ++k) diff |= KT_LOAD(kt + k) ^ u[k];
-#pragma unroll
-                        for (int k = 0; k < 8; ++k) res.w[k] = KT_LOAD(kt + 16 + k);
-                        // usable: published by an earlier launch, and this input's
-                        tab_hit = kt_state != 0u && kt_state < E.kepoch && diff == 0u;
-#undef KT_LOAD
-                    }
-                }
-                if (all_hit || tab_hit) {
-                    if (L.rec_cap) {
-                        uint32_t *rp = L.rec + lane + (size_t)(rec_at + MG_REC_HEADER) * L.N;
-#pragma unroll
-                        for (int k = 0; k < 16; ++k) rp[(size_t)k * L.N] = din[k];
-                    }
+                KcProbe P;
+                if (kc_lookup(E, cacheable, din, res, P)) {
+                    if (L.rec_cap) rec_din(L, lane, rec_at + MG_REC_HEADER, din);
                 } else {
                     res = keccak_mem(V, a.w[0], b.w[0],
                                      L.rec_cap ? L.rec + lane + (size_t)(rec_at + MG_REC_HEADER) * L.N : nullptr,
                                      L.N);
                 }
-                if (!all_hit) {
-                    const uint64_t ins = __ballot(cacheable && !hit);
-                    if (ins != 0ull && (uint32_t)__builtin_ctzll(ins) == (threadIdx.x & 63u)) {
-                        const uint32_t e = kc[KC_E * 24u + 1u] % KC_E;
-#pragma unroll
-                        for (int k = 0; k < 16; ++k) kc[e * 24u + k] = din[k];
-#pragma unroll
-                        for (int k = 0; k < 8; ++k) kc[e * 24u + 16u + k] = res.w[k];
-                        kc[KC_E * 24u] = kc[KC_E * 24u] | (1u << e);
-                        kc[KC_E * 24u + 1u] = e + 1u;
-                    }
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                    // a uniform input hashed here whose table slot read as free: the
-                    // first active lane claims the slot and, if it wins, publishes
-                    // the pair for later launches
-                    if (kt != nullptr && kt_state == 0u && (uint32_t)__builtin_ctzll(act) == (threadIdx.x & 63u)) {
-                        uint32_t expect = 0u;
-                        if (__hip_atomic_compare_exchange_strong(kt + KT_STATE, &expect, KT_BUSY, __ATOMIC_RELAXED,
-                                                                 __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-#pragma unroll
-                            for (int k = 0; k < 16; ++k) kt[k] = din[k];
-#pragma unroll
-                            for (int k = 0; k < 8; ++k) kt[16 + k] = res.w[k];
-                            __hip_atomic_store(kt + KT_STATE, E.kepoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        }
-                    }
-                }
+                kc_insert(E, cacheable, din, res, P);
                 if (L.rec_cap) {
-                    rec_head(L, lane, rec_at, MG_REC_KECCAK, b.w[0], L.steps[lane] + R.step, res);
+                    rec_head(L, lane, rec_at, MG_REC_KECCAK, b.w[0], R.step, res);
                     rec_new = rec_at + MG_REC_HEADER + ((b.w[0] + 3u) >> 2);
                 }
                 if (prof) { atomicAdd(&s_prof[256], b.w[0]); atomicAdd(&s_prof[259], b.w[0] / 136u + 1u); }
@@ -660,7 +710,7 @@ __device__ __forceinline__ void slow_step(LaneRegs &R, const StepEnv &E, uint32_
             break;
         }
         case K_CDLOAD: {  // byte (off+k) mod 2^256, 0 past the end (calldata.py:46-90,137-146)
-            const uint32_t cdl = L.calldata_len[lane];
+            const uint32_t cdl = R.cdl;
             const bool fits = u_fits32(a);
             if (fits && (a.w[0] & 3u) == 0u && (uint64_t)a.w[0] + 32u <= cdl) {
                 const uint32_t d0 = a.w[0] >> 2;
@@ -689,7 +739,7 @@ __device__ __forceinline__ void slow_step(LaneRegs &R, const StepEnv &E, uint32_
             MEMX(a, c, (int64_t)gtab_min)
             GASCOMMIT()
             ZEROFILL()
-            const uint32_t cdl = L.calldata_len[lane];
+            const uint32_t cdl = R.cdl;
             const bool bfits = u_fits32(b);
             bool wrapc = true;
 #pragma unroll
@@ -736,25 +786,19 @@ __device__ __forceinline__ void slow_step(LaneRegs &R, const StepEnv &E, uint32_
             V.set_mbyte(a.w[0], b.w[0] & 0xffu);
             break;
         case K_SLOAD: {  // over K(0) + stores (account.py:43-74)
-            const uint32_t cnt = L.storage_count[lane];
-            if (prof) atomicAdd(&s_prof[258], cnt);
-            for (uint32_t s = 0; s < cnt; ++s) {
-                const size_t base = V.row(s) * 2;
-                if (u_eq(ld_word(gv(L.storage), base), a)) { res = ld_word(gv(L.storage), base + 1); break; }
-            }
+            if (prof) atomicAdd(&s_prof[258], R.scnt);
+            storage_find<true>(V, R.scnt, a, res);
             break;
         }
         case K_SSTORE: {
-            const uint32_t cnt = L.storage_count[lane];
+            const uint32_t cnt = R.scnt;
             if (prof) atomicAdd(&s_prof[258], cnt);
-            uint32_t slot = cnt;
-            for (uint32_t s = 0; s < cnt; ++s)
-                if (u_eq(ld_word(gv(L.storage), V.row(s) * 2), a)) { slot = s; break; }
+            const uint32_t slot = storage_find<false>(V, cnt, a, res);
             if (slot == cnt && cnt >= L.storage_cap) ESCX(MG_ESC_STORAGE)
             GASCOMMIT()
             if (slot == cnt) {
                 st_word(gv(L.storage), V.row(slot) * 2, a);
-                L.storage_count[lane] = cnt + 1u;
+                L.storage_count[lane] = R.scnt = cnt + 1u;
             }
             st_word(gv(L.storage), V.row(slot) * 2 + 1, b);
             break;
@@ -830,7 +874,7 @@ __device__ __forceinline__ void slow_step(LaneRegs &R, const StepEnv &E, uint32_
     R.stop = stop;
     R.sx = sx;
     if (stop == MG_RUNNING) {
-        if (rec_new) L.rec_len[lane] = rec_new;
+        if (rec_new) L.rec_len[lane] = R.rec_len = rec_new;
         R.pc = npc; R.sp = nsp + (push ? 1u : 0u);
         R.msize = nmsize; R.depth = ndepth; R.gmin = ngmin; R.gmax = ngmax; R.fent = nfent;
     }
@@ -915,6 +959,10 @@ __device__ __noinline__ uint64_t trace_step(uint32_t *__restrict__ trace, size_t
 //   * the LDS memory window is zero past msize for the whole dispatch loop
 //     (LaneView), so MLOAD / MSTORE that grow memory inside it run inline and
 //     the general handlers zero only the HBM part of a growth;
+//   * SLOAD, SSTORE and the SHA3 of a mapping slot (64 aligned bytes) run inline
+//     too, and the lane's record length, storage count and calldata length stay
+//     in registers from the prologue on (written through when they change), so
+//     no dispatch waits on a device load of a value the kernel already had;
 //   * the prologue is a short chain of device round trips: a lane reset from the
 //     resident image keeps the image's values in registers, the lane's own loads
 //     are issued before the staging barriers, and a block stages its code from
@@ -928,7 +976,7 @@ __device__ __noinline__ uint64_t trace_step(uint32_t *__restrict__ trace, size_t
 // its own stores back (sp, msize, the counters and the trace length are zero).
 struct LaneImage {
     uint64_t gas_min, gas_max;
-    uint32_t pc, depth, status, steps;
+    uint32_t pc, depth, status, steps, storage_count;
 };
 __device__ __forceinline__ LaneImage reset_lane(const DevLanes &L, const DevResetImage &R, uint32_t lane) {
     LaneImage I;
@@ -942,7 +990,7 @@ __device__ __forceinline__ LaneImage reset_lane(const DevLanes &L, const DevRese
     L.trace_len[lane] = 0;                 // reset images start with empty traces
     L.rec_len[lane] = 0;                   // ... and empty record logs
     L.fent[lane] = MG_FENT_NONE;           // ... and no function switch yet
-    L.storage_count[lane] = cnt;
+    L.storage_count[lane] = I.storage_count = cnt;
     for (uint32_t s = 0; s < cnt; ++s) {
         const size_t idx = ((size_t)s * L.N + lane) * 4;
         // one entry's four loads in flight together
@@ -955,14 +1003,14 @@ __device__ __forceinline__ LaneImage reset_lane(const DevLanes &L, const DevRese
 // The lane constant an environment opcode of the run set pushes (run_table.h
 // env_push; `instr`: the opcode's instruction index, for PC).
 DEV U256 env_word(const LaneView &V, const DevCode &C, const uint32_t *a32, uint32_t op, uint32_t instr,
-                  uint32_t msize) {
+                  uint32_t msize, uint32_t cdl) {
     switch (op) {
     case 0x30: return V.env(0);                          // ADDRESS
     case 0x32: return V.env(2);                          // ORIGIN
     case 0x33: return V.env(1);                          // CALLER
     case 0x34: return V.env(3);                          // CALLVALUE
     case 0x3a: return V.env(4);                          // GASPRICE
-    case 0x36: return u_small(V.L.calldata_len[V.lane]);
+    case 0x36: return u_small(cdl);
     case 0x38: return u_small(C.n_bytes);                // CODESIZE
     case 0x45: return u_small(MG_MSTATE_GAS_LIMIT);
     case 0x58: return u_small(a32[C.addr_off + instr]);
@@ -1074,14 +1122,19 @@ __global__ __launch_bounds__(LANE_BLOCK) void k_lane_step(DevLanes L, const DevC
     uint32_t tlen = 0;                                    // trace length (BoundedLoops)
     uint32_t fent = MG_FENT_NONE;                         // last function-entry landing
     uint32_t steps0 = 0;                                  // L.steps at entry
+    // the lane's counts, kept here across the dispatch loop (LaneRegs): no handler
+    // waits on a device load for them
+    uint32_t rec_len = 0, scnt = 0, cdl = 0;
     const uint32_t loop_on = kLoop ? loop_bound : 0u;     // kernel argument: uniform
     uint64_t txlim = 0, gmin = 0, gmax = 0;
     if (run_st) {
         C = codes[my_code];
         flags = L.flags[lane];
         txlim = L.gas_limit[lane];
+        cdl = L.calldata_len[lane];
         if (from_image) {
             pc = I.pc; depth = I.depth; gmin = I.gas_min; gmax = I.gas_max; steps0 = I.steps;
+            scnt = I.storage_count;                       // and an empty record log
         } else {
             pc = L.pc[lane]; sp = L.sp[lane]; msize = L.msize[lane]; depth = L.depth[lane];
             fent = L.fent[lane];
@@ -1089,6 +1142,7 @@ __global__ __launch_bounds__(LANE_BLOCK) void k_lane_step(DevLanes L, const DevC
             gmin = L.gas_min[lane]; gmax = L.gas_max[lane];
             // the counters are kept absolute: the epilogue stores them, no read-modify-write
             steps0 = L.steps[lane]; n_sha3 = L.sha3_count[lane]; n_exp = L.exp_count[lane];
+            rec_len = L.rec_len[lane]; scnt = L.storage_count[lane];
         }
     }
     for (uint32_t i = threadIdx.x; i < 256u; i += blockDim.x) s_dec[i] = kDec[i];
@@ -1347,7 +1401,7 @@ __global__ __launch_bounds__(LANE_BLOCK) void k_lane_step(DevLanes L, const DevC
                                 break;
                             }
                             case K_ENV:
-                                V.set_wstack(s, env_word(V, C, a32, rop, upc + k, msize));
+                                V.set_wstack(s, env_word(V, C, a32, rop, upc + k, msize, cdl));
                                 ++s;
                                 break;
                             case K_POP:
@@ -1434,7 +1488,7 @@ __global__ __launch_bounds__(LANE_BLOCK) void k_lane_step(DevLanes L, const DevC
                                 break;
                             }
                             case K_ENV: {
-                                const U256 v = env_word(V, C, a32, rop, upc + k, msize);
+                                const U256 v = env_word(V, C, a32, rop, upc + k, msize, cdl);
                                 if (sp >= 2u) V.set_stack(sp - 2u, T1);
                                 T1 = T0; T0 = v; ++sp;
                                 break;
@@ -1601,7 +1655,7 @@ __global__ __launch_bounds__(LANE_BLOCK) void k_lane_step(DevLanes L, const DevC
                 case 0x33: r = V.env(1); break;                 // CALLER
                 case 0x34: r = V.env(3); break;                 // CALLVALUE
                 case 0x3a: r = V.env(4); break;                 // GASPRICE
-                case 0x36: r = u_small(L.calldata_len[lane]); break;
+                case 0x36: r = u_small(cdl); break;
                 case 0x38: r = u_small(C.n_bytes); break;       // CODESIZE
                 case 0x45: r = u_small(MG_MSTATE_GAS_LIMIT); break;
                 case 0x58: r = u_small(a32[C.addr_off + pc]); break;
@@ -1616,7 +1670,7 @@ __global__ __launch_bounds__(LANE_BLOCK) void k_lane_step(DevLanes L, const DevC
         // gmin + fee <= the machine-state limit, then GASCOMMIT's + table gas < glim
         case K_MLOAD: {
             uint32_t nms, fee;
-            ok = sp >= 1u && mem_fast(T0, msize, grow_lim, nms, fee) &&
+            ok = sp >= 1u && mem_fast(T0, 32u, msize, grow_lim, nms, fee) &&
                  gmin + fee <= MG_MSTATE_GAS_LIMIT && ngmin + fee < glim;
             if (ok) {
                 msize = nms;
@@ -1627,7 +1681,7 @@ __global__ __launch_bounds__(LANE_BLOCK) void k_lane_step(DevLanes L, const DevC
         }
         case K_MSTORE: {
             uint32_t nms, fee;
-            ok = sp >= 2u && mem_fast(T0, msize, grow_lim, nms, fee) &&
+            ok = sp >= 2u && mem_fast(T0, 32u, msize, grow_lim, nms, fee) &&
                  gmin + fee <= MG_MSTATE_GAS_LIMIT && ngmin + fee < glim;
             if (ok) {
                 msize = nms;
@@ -1638,8 +1692,74 @@ __global__ __launch_bounds__(LANE_BLOCK) void k_lane_step(DevLanes L, const DevC
             }
             break;
         }
+        // SHA3 of a mapping slot: 64 bytes at an aligned offset, inside msize or growing
+        // memory inside the window (mem_fast), with the general path's checks in its
+        // order: gas 30 + 6 * 2 against glim, then mem_extend's fee against the
+        // machine-state limit alone; the record's room is decided before any write
+        case K_SHA3: {
+            uint32_t nms, fee;
+            ok = sp >= 2u && u_fits32(T1) && T1.w[0] == 64u && (T0.w[0] & 3u) == 0u &&
+                 mem_fast(T0, 64u, msize, grow_lim, nms, fee) && gmin + 42u < glim &&
+                 gmin + 42u + fee <= MG_MSTATE_GAS_LIMIT &&
+                 (!L.rec_cap || rec_len + MG_REC_HEADER + 16u <= L.rec_cap);
+            if (ok) {
+                const uint32_t d0 = T0.w[0] >> 2;
+                uint32_t din[16];
+                if (d0 + 16u <= mw) {
+#pragma unroll
+                    for (int k = 0; k < 16; ++k) din[k] = V.lmdw(d0 + (uint32_t)k);
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 16; ++k) din[k] = V.mdw(d0 + (uint32_t)k);
+                }
+                U256 r;
+                KcProbe P;
+                if (!kc_lookup(E, true, din, r, P)) keccak64(din, r.w);
+                kc_insert(E, true, din, r, P);
+                if (L.rec_cap) {
+                    rec_din(L, lane, rec_len + MG_REC_HEADER, din);
+                    rec_len = rec_head(L, lane, rec_len, MG_REC_KECCAK, 64u, steps0 + executed - 1u, r) + 16u;
+                    L.rec_len[lane] = rec_len;
+                }
+                if (prof) { atomicAdd(&s_prof[256], 64u); atomicAdd(&s_prof[259], 1u); }
+                ++n_sha3;
+                msize = nms;
+                T0 = r;
+                T1 = sp >= 3u ? V.stack(sp - 3u) : u_zero();
+                --sp; ++pc; gmin += 42u + fee; gmax += 42u + fee;
+            }
+            break;
+        }
+        // SLOAD / SSTORE on the table gas.  Underflow, write protection, a full table
+        // and out of gas are the general handler's
+        case K_SLOAD:
+            ok = gas_ok && sp >= 1u;
+            if (ok) {
+                if (prof) atomicAdd(&s_prof[258], scnt);
+                U256 r;
+                storage_find<true>(V, scnt, T0, r);
+                T0 = r; ++pc; gmin = ngmin; gmax = ngmax;
+            }
+            break;
+        case K_SSTORE:
+            if (gas_ok && sp >= 2u && !(flags & MG_LANE_STATIC)) {
+                U256 none;
+                const uint32_t slot = storage_find<false>(V, scnt, T0, none);
+                ok = slot < scnt || scnt < L.storage_cap;
+                if (ok) {
+                    if (prof) atomicAdd(&s_prof[258], scnt);
+                    if (slot == scnt) {
+                        st_word(gv(L.storage), V.row(slot) * 2, T0);
+                        L.storage_count[lane] = ++scnt;
+                    }
+                    st_word(gv(L.storage), V.row(slot) * 2 + 1, T1);
+                    T0 = sp >= 3u ? V.stack(sp - 3u) : u_zero();
+                    T1 = sp >= 4u ? V.stack(sp - 4u) : u_zero();
+                    sp -= 2u; ++pc; gmin = ngmin; gmax = ngmax;
+                }
+            }
+            break;
         case K_CDLOAD: {                // aligned and inside the calldata
-            const uint32_t cdl = L.calldata_len[lane];
             ok = gas_ok && sp >= 1u && u_fits32(T0) && (T0.w[0] & 3u) == 0u &&
                  (uint64_t)T0.w[0] + 32u <= cdl;
             if (ok) {
@@ -1656,9 +1776,11 @@ __global__ __launch_bounds__(LANE_BLOCK) void k_lane_step(DevLanes L, const DevC
         }
 #undef PUSHV
         if (!ok) {
-            LaneRegs R{T0, T1, gmin, gmax, pc, sp, msize, depth, n_sha3, n_exp, 0u, 0u, executed - 1u, fent};
+            LaneRegs R{T0, T1, gmin, gmax, pc, sp, msize, depth, n_sha3, n_exp, 0u, 0u, steps0 + executed - 1u, fent,
+                       rec_len, scnt, cdl};
             slow_step(R, E, uk, ux);
             n_sha3 = R.n_sha3; n_exp = R.n_exp;
+            rec_len = R.rec_len; scnt = R.scnt;     // changed only by an instruction that completed
             if (R.stop != MG_RUNNING) {
                 status = R.stop;
                 aux = R.sx;

@@ -1075,7 +1075,11 @@ __global__ __launch_bounds__(256) void k_sym_step(DevLanes L, DevSym S, DevTaint
             if (kind == K_SWAP && sp >= nin) { t_in0 = sym_tag(S, N, lane, sp - 1u); t_in1 = sym_tag(S, N, lane, sp - nin); }
         }
         LaneRegs R{sp >= 1u ? V.stack(sp - 1u) : u_zero(), sp >= 2u ? V.stack(sp - 2u) : u_zero(), gmin, gmax,
-                   pc, sp, msize, depth, n_sha3, n_exp, 0u, 0u, executed, fent};
+                   pc, sp, msize, depth, n_sha3, n_exp, 0u, 0u, 0u, fent, 0u, 0u, 0u};
+        // the lane's counts live in memory here: read for the handlers that use them
+        if (kind == K_SHA3 || kind == K_ALU) { R.step = L.steps[lane] + executed; R.rec_len = L.rec_len[lane]; }
+        if (kind == K_SLOAD || kind == K_SSTORE) R.scnt = L.storage_count[lane];
+        if (kind == K_ENV || kind == K_CDLOAD || kind == K_CDCOPY) R.cdl = L.calldata_len[lane];
         const U256 pa = R.T0, pb = R.T1;
         const uint32_t sp0 = sp;
         slow_step(R, E, uy, d.x);
